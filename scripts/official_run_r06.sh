@@ -24,5 +24,5 @@ python $R/scripts/rocprof_summary.py /tmp/kts/kts_results.db $O/r06_train_serial
  cd $R && python scripts/train_bench.py --batch 32 --steps 4 --warmup 2 --dtype bf16 --no-fused-attn 2>/dev/null | tail -1;
  cd $R && python scripts/train_bench.py --batch 32 --steps 4 --warmup 2 --dtype f16 2>/dev/null | tail -1) | tee $O/r06_train_step.json
 (cd $R && bash scripts/run_sweep.sh 2>/dev/null | tail -12)
-(cd $R && python bench.py --error-budget --kernels-json $O/r06_kernels_hip_events.json > $O/r06_bench.json 2> $O/bench.err; tail -c 1800 $O/r06_bench.json)
+(cd $R && python bench.py --full --error-budget --kernels-json $O/r06_kernels_hip_events.json > $O/r06_bench.json 2> $O/bench.err; tail -c 1800 $O/r06_bench.json)
 ls -la $O | tail -40

@@ -5,6 +5,6 @@
 #   bash scripts/scale.sh [outdir] [gpus...]        default: gpurun_out/scale  1 2 4 8
 R=$(cd "$(dirname "$0")/.." && pwd); O=${1:-$R/gpurun_out/scale}; shift; NS=${@:-1 2 4 8}; mkdir -p $O; cd $R
 for n in $NS; do
-  python bench.py --gpus $n --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_n$n.json 2> $O/bench_n$n.err
+  python bench.py --full --gpus $n --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_n$n.json 2> $O/bench_n$n.err
   python scripts/print_bench.py $O/bench_n$n.json 2>/dev/null | tail -3
 done

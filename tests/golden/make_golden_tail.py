@@ -108,14 +108,18 @@ def optim_digest(osd):
 
 def write_reference_style_checkpoint(path, prefix):
     """The file both sides must agree on, built ONLY with our code: tiny32 model with synthetic weights, one AdamW step on a fixed
-    synthetic gradient (so exp_avg / exp_avg_sq / step are non-trivial), saved by uformer_amd.checkpoint.save_training_state."""
+    synthetic gradient (so exp_avg / exp_avg_sq / step are non-trivial), saved by uformer_amd.checkpoint.save_training_state.
+    The step is torch's fused CPU AdamW: the digests compare bytes, and the default AdamW's square root of exp_avg_sq (torch.sqrt on
+    a large CPU tensor, handed to MKL's vector math) gave different last bits on an Intel and an AMD host; the fused kernel's square
+    root is exactly rounded and gave the same bytes on both."""
     from uformer_amd import checkpoint as ck
     from uformer_amd import model as um
     cfg = spec.arch_config("tiny32", img_size=128)
     m = um.Uformer(img_size=cfg.img_size, embed_dim=cfg.embed_dim, depths=list(cfg.depths), num_heads=list(cfg.num_heads), modulator=cfg.modulator,
                    dd_in=cfg.dd_in, compute_dtype=torch.float32)
     m.load_state_dict(spec.synth_state_dict(cfg, 77), strict=True)
-    opt = torch.optim.AdamW(m.parameters(), lr=1.5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.02)     # train/train_denoise.py:77 form
+    opt = torch.optim.AdamW(m.parameters(), lr=1.5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.02,      # train/train_denoise.py:77 form
+                            fused=True)
     gen = torch.Generator().manual_seed(78)
     for p in m.parameters():
         p.grad = 1e-3 * torch.randn(p.shape, generator=gen)
