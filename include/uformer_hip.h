@@ -487,6 +487,11 @@ int uf_batch_ssim(const float* a, const float* b, float* ssim_per_image, int n_i
  * test/test_sidd.py:108-109). */
 int uf_expand2square(const float* img, float* canvas, float* mask, int B, int C, int h, int w, int X, void* stream);
 int uf_crop_clamp(const float* canvas, float* out, int B, int C, int h, int w, int X, int clamp01, void* stream);
+/* The same on a rectangular canvas (B,C,Xh,Xw), Xh >= h and Xw >= w: the image at ((Xh-h)/2, (Xw-w)/2), the placement rule of
+ * expand2square applied to each axis on its own; mask (B,1,Xh,Xw) may be NULL.  With Xh = Xw = X these are uf_expand2square /
+ * uf_crop_clamp. */
+int uf_expand_canvas(const float* img, float* canvas, float* mask, int B, int C, int h, int w, int Xh, int Xw, void* stream);
+int uf_crop_clamp_canvas(const float* canvas, float* out, int B, int C, int h, int w, int Xh, int Xw, int clamp01, void* stream);
 
 /* ---- f-4: training input pipeline on the device ---------------------------------------------------------------------
  * DataLoaderTrain.__getitem__ (dataset/dataset_denoise.py:42-73) for a whole batch: out[b] = T_k(frame[idx][:, r0:r0+ps,
@@ -515,7 +520,8 @@ typedef struct uf_model_desc {
 } uf_model_desc;
 
 size_t uf_uformer_workspace_bytes(const uf_model_desc* d, int B, int H, int W, uf_dtype dtype);
-/* img, out: f32 NCHW (B,dd_in,H,W) / (B,in_chans,H,W).  H == W, multiple of 128.
+/* img, out: f32 NCHW (B,dd_in,H,W) / (B,in_chans,H,W).  H and W each a positive multiple of 128 (H != W allowed; stage s runs
+ * at (H / 2^k, W / 2^k)).
  * All work is ordered on `stream`: for B >= 8 the library cuts the batch in two and runs the second half on an
  * internal side stream forked from / joined back into `stream` with events (kernel ramps and tails of the halves
  * overlap; results are bit-identical); UF_STREAMS=1 in the environment turns that off, UF_STREAMS=n (<= 8) forces n. */

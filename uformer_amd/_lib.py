@@ -145,6 +145,8 @@ SIGNATURES = {
     "uf_batch_ssim": (I, [P, P, P, I, I, I, I, P, c_size_t, P]),
     "uf_expand2square": (I, [P, P, P, I, I, I, I, I, P]),
     "uf_crop_clamp": (I, [P, P, I, I, I, I, I, I, P]),
+    "uf_expand_canvas": (I, [P, P, P, I, I, I, I, I, I, P]),
+    "uf_crop_clamp_canvas": (I, [P, P, I, I, I, I, I, I, I, P]),
     "uf_crop_augment": (I, [P, I, I, P, P, I, I, I, I, I, P]),
     "uf_mixup": (I, [P, P, P, P, I, C.c_longlong, P]),
     "uf_uformer_workspace_bytes": (c_size_t, [C.POINTER(ModelDesc), I, I, I, I]),

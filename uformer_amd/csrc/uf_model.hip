@@ -213,7 +213,8 @@ extern "C" int uf_upsample_fwd(const float* x, int ld_x, const void* w, const fl
 namespace {
 struct Plan {
     int C[9];        // block width per stage
-    int res[9];      // H (=W) per stage
+    int res_h[9];    // H per stage
+    int res_w[9];    // W per stage
     size_t M[9];     // tokens per stage
     size_t off_D[4]; // byte offsets of the decoder concat buffers D0..D3 (f32 [M][2*Cskip])
     size_t off_P;    // bottleneck stream
@@ -224,8 +225,8 @@ struct Plan {
 
 int make_plan(Plan& pl, const uf_model_desc* d, int B, int H, int W, uf_dtype dtype) {
     UF_REQUIRE(d, UF_ERR_NULL, "model desc is null");
-    UF_REQUIRE(H == W, UF_ERR_SHAPE, "Uformer needs square inputs (reference takes sqrt(L), model.py:910-911): H=%d W=%d", H, W);
-    UF_REQUIRE(H % 128 == 0 && H > 0, UF_ERR_SHAPE, "H=W=%d must be a multiple of 128 (4 downsamplings x window 8)", H);
+    UF_REQUIRE(H % 128 == 0 && H > 0, UF_ERR_SHAPE, "H=%d must be a positive multiple of 128 (4 downsamplings x window 8)", H);
+    UF_REQUIRE(W % 128 == 0 && W > 0, UF_ERR_SHAPE, "W=%d must be a positive multiple of 128 (4 downsamplings x window 8)", W);
     UF_REQUIRE(B > 0, UF_ERR_SHAPE, "B=%d", B);
     UF_REQUIRE(d->embed_dim >= 16 && d->embed_dim % 16 == 0, UF_ERR_SHAPE, "embed_dim=%d must be a multiple of 16", d->embed_dim);
     const int e = d->embed_dim;
@@ -234,8 +235,9 @@ int make_plan(Plan& pl, const uf_model_desc* d, int B, int H, int W, uf_dtype dt
     size_t blk = 0;
     for (int s = 0; s < 9; ++s) {
         pl.C[s] = e * mult[s];
-        pl.res[s] = H / div[s];
-        pl.M[s] = (size_t)B * pl.res[s] * pl.res[s];
+        pl.res_h[s] = H / div[s];
+        pl.res_w[s] = W / div[s];
+        pl.M[s] = (size_t)B * pl.res_h[s] * pl.res_w[s];
         const size_t b = block_ws_bytes(pl.M[s], pl.C[s], dtype);
         if (b > blk) blk = b;
     }
@@ -290,7 +292,7 @@ int forward_one_stream(const uf_model_desc* d, const float* img, float* out, int
     // in round 3 -- profiles/r03_chunk_ab.txt -- and is gone.)
     auto run_stage = [&](int s, float* x, int ld) -> int {
         for (int i = 0; i < d->depths[s]; ++i, ++blk) {
-            int r = uf_lewin_block_fwd(blk, x, ld, B, pl.res[s], pl.res[s], pl.C[s], nullptr, 0, dtype, bws, pl.blk_bytes, st);
+            int r = uf_lewin_block_fwd(blk, x, ld, B, pl.res_h[s], pl.res_w[s], pl.C[s], nullptr, 0, dtype, bws, pl.blk_bytes, st);
             if (r) return r;
         }
         return UF_OK;
@@ -305,7 +307,7 @@ int forward_one_stream(const uf_model_desc* d, const float* img, float* out, int
         if (rc) return rc;
         float* nx; int nld;
         if (s < 3) enc_view(s + 1, nx, nld); else { nx = P; nld = pl.C[4]; }
-        rc = uf_downsample_fm_fwd(x, ld, d->down_w[s], d->down_w_fm[s], d->down_b[s], nx, nld, B, pl.res[s], pl.res[s], pl.C[s], dtype, st);
+        rc = uf_downsample_fm_fwd(x, ld, d->down_w[s], d->down_w_fm[s], d->down_b[s], nx, nld, B, pl.res_h[s], pl.res_w[s], pl.C[s], dtype, st);
         if (rc) return rc;
         x = nx; ld = nld;
     }
@@ -314,7 +316,7 @@ int forward_one_stream(const uf_model_desc* d, const float* img, float* out, int
     for (int k = 0; k < 4; ++k) {  // decoder, model.py:1287-1301
         const int s = 5 + k;
         const int cin = pl.C[s - 1], cout = pl.C[s] / 2;
-        rc = uf_upsample_fwd(x, ld, d->up_w[k], d->up_b[k], D[k], pl.C[s], B, pl.res[s - 1], pl.res[s - 1], cin, cout, dtype, st);
+        rc = uf_upsample_fwd(x, ld, d->up_w[k], d->up_b[k], D[k], pl.C[s], B, pl.res_h[s - 1], pl.res_w[s - 1], cin, cout, dtype, st);
         if (rc) return rc;
         x = D[k]; ld = pl.C[s];
         rc = run_stage(s, x, ld);

@@ -218,23 +218,24 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float* __restrict__ a, 
 }
 
 // ---- expand2square / crop + clamp ------------------------------------------------------------------------------------
-// canvas (B,C,X,X) = 0 except the image at (y0,x0); mask (B,1,X,X) = 1 over the image        (test/test_sidd.py:79-92)
+// canvas (B,C,Xh,Xw) = 0 except the image at (y0,x0); mask (B,1,Xh,Xw) = 1 over the image  (test/test_sidd.py:79-92; Xh = Xw for expand2square)
 __global__ __launch_bounds__(256) void pad_canvas_kernel(const float* __restrict__ img, float* __restrict__ canvas, float* __restrict__ mask, int BC, int C, int h, int w,
-                                                         int X, int y0, int x0) {
-    const long long n = (long long)BC * X * X;
+                                                         int Xh, int Xw, int y0, int x0) {
+    const long long n = (long long)BC * Xh * Xw;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const int xx = (int)(i % X), yy = (int)((i / X) % X), pc = (int)(i / ((long long)X * X));
+        const int xx = (int)(i % Xw), yy = (int)((i / Xw) % Xh), pc = (int)(i / ((long long)Xh * Xw));
         const bool in = yy >= y0 && yy < y0 + h && xx >= x0 && xx < x0 + w;
         canvas[i] = in ? img[((size_t)pc * h + (yy - y0)) * w + (xx - x0)] : 0.f;
-        if (mask && pc % C == 0) mask[((size_t)(pc / C) * X + yy) * X + xx] = in ? 1.f : 0.f;
+        if (mask && pc % C == 0) mask[((size_t)(pc / C) * Xh + yy) * Xw + xx] = in ? 1.f : 0.f;
     }
 }
 // out (B,C,h,w) = clamp(canvas[:, :, y0:y0+h, x0:x0+w], 0, 1)                               (test/test_sidd.py:108-109)
-__global__ __launch_bounds__(256) void crop_clamp_kernel(const float* __restrict__ canvas, float* __restrict__ out, int BC, int h, int w, int X, int y0, int x0, int clamp01) {
+__global__ __launch_bounds__(256) void crop_clamp_kernel(const float* __restrict__ canvas, float* __restrict__ out, int BC, int h, int w, int Xh, int Xw, int y0, int x0,
+                                                         int clamp01) {
     const long long n = (long long)BC * h * w;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const int xx = (int)(i % w), yy = (int)((i / w) % h), pc = (int)(i / ((long long)w * h));
-        float v = canvas[((size_t)pc * X + y0 + yy) * X + x0 + xx];
+        float v = canvas[((size_t)pc * Xh + y0 + yy) * Xw + x0 + xx];
         if (clamp01) v = fminf(fmaxf(v, 0.f), 1.f);
         out[i] = v;
     }
@@ -466,27 +467,42 @@ extern "C" int uf_batch_ssim(const float* a, const float* b, float* ssim_per_ima
     return check_launch("batch_ssim");
 }
 
-extern "C" int uf_expand2square(const float* img, float* canvas, float* mask, int B, int C, int h, int w, int X, void* stream) {
-    UF_REQUIRE(img && canvas, UF_ERR_NULL, "uf_expand2square: null pointer");
-    UF_REQUIRE(B > 0 && C > 0 && h > 0 && w > 0 && X >= h && X >= w, UF_ERR_SHAPE, "uf_expand2square: B=%d C=%d h=%d w=%d X=%d", B, C, h, w, X);
-    const long long n = (long long)B * C * X * X;
+namespace {
+int expand_canvas(const float* img, float* canvas, float* mask, int B, int C, int h, int w, int Xh, int Xw, void* stream, const char* name) {
+    UF_REQUIRE(img && canvas, UF_ERR_NULL, "%s: null pointer", name);
+    UF_REQUIRE(B > 0 && C > 0 && h > 0 && w > 0 && Xh >= h && Xw >= w, UF_ERR_SHAPE, "%s: B=%d C=%d h=%d w=%d Xh=%d Xw=%d", name, B, C, h, w, Xh, Xw);
+    const long long n = (long long)B * C * Xh * Xw;
     hipStream_t st = (hipStream_t)stream;
     {
-        ScopedTimer tm("expand2square", 0.0, 4.0 * n + 4.0 * B * C * h * w, st);
-        hipLaunchKernelGGL(pad_canvas_kernel, dim3(grid_for(n, 1024)), dim3(256), 0, st, img, canvas, mask, B * C, C, h, w, X, (X - h) / 2, (X - w) / 2);
+        ScopedTimer tm(name + 3, 0.0, 4.0 * n + 4.0 * B * C * h * w, st);
+        hipLaunchKernelGGL(pad_canvas_kernel, dim3(grid_for(n, 1024)), dim3(256), 0, st, img, canvas, mask, B * C, C, h, w, Xh, Xw, (Xh - h) / 2, (Xw - w) / 2);
     }
-    return check_launch("expand2square");
+    return check_launch(name + 3);
 }
-extern "C" int uf_crop_clamp(const float* canvas, float* out, int B, int C, int h, int w, int X, int clamp01, void* stream) {
-    UF_REQUIRE(canvas && out, UF_ERR_NULL, "uf_crop_clamp: null pointer");
-    UF_REQUIRE(B > 0 && C > 0 && h > 0 && w > 0 && X >= h && X >= w, UF_ERR_SHAPE, "uf_crop_clamp: B=%d C=%d h=%d w=%d X=%d", B, C, h, w, X);
+int crop_clamp_canvas(const float* canvas, float* out, int B, int C, int h, int w, int Xh, int Xw, int clamp01, void* stream, const char* name) {
+    UF_REQUIRE(canvas && out, UF_ERR_NULL, "%s: null pointer", name);
+    UF_REQUIRE(B > 0 && C > 0 && h > 0 && w > 0 && Xh >= h && Xw >= w, UF_ERR_SHAPE, "%s: B=%d C=%d h=%d w=%d Xh=%d Xw=%d", name, B, C, h, w, Xh, Xw);
     const long long n = (long long)B * C * h * w;
     hipStream_t st = (hipStream_t)stream;
     {
-        ScopedTimer tm("crop_clamp", 0.0, 8.0 * n, st);
-        hipLaunchKernelGGL(crop_clamp_kernel, dim3(grid_for(n, 1024)), dim3(256), 0, st, canvas, out, B * C, h, w, X, (X - h) / 2, (X - w) / 2, clamp01);
+        ScopedTimer tm(name + 3, 0.0, 8.0 * n, st);
+        hipLaunchKernelGGL(crop_clamp_kernel, dim3(grid_for(n, 1024)), dim3(256), 0, st, canvas, out, B * C, h, w, Xh, Xw, (Xh - h) / 2, (Xw - w) / 2, clamp01);
     }
-    return check_launch("crop_clamp");
+    return check_launch(name + 3);
+}
+}  // namespace
+
+extern "C" int uf_expand2square(const float* img, float* canvas, float* mask, int B, int C, int h, int w, int X, void* stream) {
+    return expand_canvas(img, canvas, mask, B, C, h, w, X, X, stream, "uf_expand2square");
+}
+extern "C" int uf_crop_clamp(const float* canvas, float* out, int B, int C, int h, int w, int X, int clamp01, void* stream) {
+    return crop_clamp_canvas(canvas, out, B, C, h, w, X, X, clamp01, stream, "uf_crop_clamp");
+}
+extern "C" int uf_expand_canvas(const float* img, float* canvas, float* mask, int B, int C, int h, int w, int Xh, int Xw, void* stream) {
+    return expand_canvas(img, canvas, mask, B, C, h, w, Xh, Xw, stream, "uf_expand_canvas");
+}
+extern "C" int uf_crop_clamp_canvas(const float* canvas, float* out, int B, int C, int h, int w, int Xh, int Xw, int clamp01, void* stream) {
+    return crop_clamp_canvas(canvas, out, B, C, h, w, Xh, Xw, clamp01, stream, "uf_crop_clamp_canvas");
 }
 
 extern "C" int uf_crop_augment(const void* src, int src_is_u8, int src_hwc, float* out, const int* meta, int B, int N, int H, int W, int ps, void* stream) {

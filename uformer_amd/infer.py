@@ -3,10 +3,11 @@
 ``restore``: exactly the steps the reference's evaluation scripts put around ``Uformer.forward`` -- ``expand2square`` to a square
 multiple of 128 (test/test_sidd.py:79-92), forward, ``masked_select`` crop, clamp (:106-109; test/test_gopro_hide.py:77-103) -- with
 the pad and the crop + clamp each ONE kernel on the device (``uf_expand2square``, ``uf_crop_clamp``); parity-exact with the
-reference pipeline.
+reference pipeline.  ``restore(..., canvas="rect")`` pads each side to its own multiple of 128 instead (``uf_expand_canvas``,
+``uf_crop_clamp_canvas``): less padding, but not the reference's protocol.
 
 ``restore_tiled``: a capability the reference does not have.  A 1280x720 frame padded to 1280x1280 computes 1.78x the pixels it
-needs; here the frame is covered by overlapping SQUARE tiles (the model needs H == W, multiples of 128) that are restored
+needs; here the frame is covered by overlapping SQUARE tiles (multiples of 128) that are restored
 independently -- as one batch -- and cross-faded over the overlap.  It is an approximation of the full-frame result (a tile's
 border pixels see zero padding / a cut context instead of the neighbouring image), which is why it is opt-in and why the overlap is
 wide; ``restore`` stays the reference-exact path.
@@ -37,14 +38,27 @@ def crop_to_mask(restored: Tensor, h: int, w: int, clamp: bool = False) -> Tenso
 
 
 @torch.no_grad()
-def restore(model, img: Tensor, factor: float = 128.0, clamp: bool = True) -> Tensor:
-    """Restore images of any (h, w): pad to a square multiple of ``factor``, run ``model``, crop back, clamp to [0,1]
-    (test/test_sidd.py:106-109).  ``img``: (B,3,h,w) float32 on the model's device."""
+def restore(model, img: Tensor, factor: float = 128.0, clamp: bool = True, canvas: str = "square") -> Tensor:
+    """Restore images of any (h, w): pad to a canvas of multiples of ``factor``, run ``model``, crop back, clamp to [0,1]
+    (test/test_sidd.py:106-109).  ``img``: (B,3,h,w) float32 on the model's device.
+
+    ``canvas="square"`` (default): the reference's protocol -- ``expand2square``, one square side X = max(h, w) rounded up to a
+    multiple of ``factor``; output identical to the reference pipeline.
+    ``canvas="rect"``: each side rounded up to its OWN multiple of ``factor`` (a 720 x 1280 frame runs on 768 x 1280 instead of
+    1280 x 1280, 40 % fewer pixels), the image centred the same way on each axis.  This is the reference network's math on a
+    different canvas: the convolutions and the windows at the image border see less zero padding, so the output DIFFERS from the
+    reference's square-padded result.  The two are equal only when both canvases coincide (e.g. 200 x 136 -> 256 x 256 either way)."""
     if img.dim() != 4:
         raise ValueError(f"restore expects (B,C,h,w), got {tuple(img.shape)}")
     h, w = img.shape[-2:]
-    padded, _ = ops.expand2square(img, factor, with_mask=False)
-    return ops.crop_clamp(model(padded), h, w, clamp)
+    if canvas == "square":
+        padded, _ = ops.expand2square(img, factor, with_mask=False)
+        return ops.crop_clamp(model(padded), h, w, clamp)
+    if canvas == "rect":
+        Xh, Xw = int(math.ceil(h / float(factor)) * factor), int(math.ceil(w / float(factor)) * factor)
+        padded, _ = ops.expand_canvas(img, Xh, Xw, with_mask=False)
+        return ops.crop_clamp_canvas(model(padded), h, w, clamp)
+    raise ValueError(f"restore: canvas must be 'square' or 'rect', got {canvas!r}")
 
 
 def _starts(n: int, tile: int, min_overlap: int) -> List[int]:

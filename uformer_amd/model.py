@@ -17,8 +17,7 @@ within the 1e-3 output tolerance; train it under a loss scale as the reference d
 """
 from __future__ import annotations
 
-import math
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -26,8 +25,10 @@ import torch.nn as nn
 from . import _lib, ops, packing
 from ._lib import UformerHipError
 from .spec import STAGES, UformerConfig, relative_position_index
+from .train import block_hw
 
 Tensor = torch.Tensor
+HW = Optional[Tuple[int, int]]    # (H, W) of a token map; the module forwards take it as the keyword ``hw`` (None: the square side of L)
 
 
 def window_partition(x: Tensor, win_size: int, dilation_rate: int = 1) -> Tensor:
@@ -139,16 +140,16 @@ class LeFF(nn.Module):
         self.dim = dim
         self.hidden_dim = hidden_dim
 
-    def forward(self, x: Tensor, compute_dtype=torch.float32) -> Tensor:
-        bs, hw, c = x.shape
-        hh = int(math.sqrt(hw))
-        a = _to_compute(x.reshape(bs * hw, c), compute_dtype)
+    def forward(self, x: Tensor, compute_dtype=torch.float32, *, hw: HW = None) -> Tensor:
+        bs, L, c = x.shape
+        H, W = block_hw(L, hw, "LeFF")
+        a = _to_compute(x.reshape(bs * L, c), compute_dtype)
         h1 = ops.linear(a, _to_compute(self.linear1[0].weight, compute_dtype), self.linear1[0].bias.detach().float(), 1)
-        h2 = ops.dwconv3x3_gelu(h1.reshape(bs, hh, hh, self.hidden_dim), packing.pack_dwconv(self.dwconv[0].weight),
+        h2 = ops.dwconv3x3_gelu(h1.reshape(bs, H, W, self.hidden_dim), packing.pack_dwconv(self.dwconv[0].weight),
                                 self.dwconv[0].bias.detach().float())
-        y = ops.linear(h2.reshape(bs * hw, self.hidden_dim), _to_compute(self.linear2[0].weight, compute_dtype),
+        y = ops.linear(h2.reshape(bs * L, self.hidden_dim), _to_compute(self.linear2[0].weight, compute_dtype),
                        self.linear2[0].bias.detach().float(), 0)
-        return y.reshape(bs, hw, c).to(x.dtype)
+        return y.reshape(bs, L, c).to(x.dtype)
 
     def flops(self, H, W):
         return H * W * self.dim * self.hidden_dim + H * W * self.hidden_dim * 9 + H * W * self.hidden_dim * self.dim
@@ -163,9 +164,9 @@ class Downsample(nn.Module):
         self.in_channel = in_channel
         self.out_channel = out_channel
 
-    def forward(self, x: Tensor, compute_dtype=torch.float32) -> Tensor:
+    def forward(self, x: Tensor, compute_dtype=torch.float32, *, hw: HW = None) -> Tensor:
         B, L, Cc = x.shape
-        H = W = int(math.sqrt(L))
+        H, W = block_hw(L, hw, "Downsample")
         y = ops.downsample(x.reshape(B * L, Cc), packing.pack_downsample(self.conv[0].weight, compute_dtype),
                            self.conv[0].bias.detach().float(), B, H, W)
         return y.reshape(B, L // 4, self.out_channel)
@@ -183,9 +184,9 @@ class Upsample(nn.Module):
         self.in_channel = in_channel
         self.out_channel = out_channel
 
-    def forward(self, x: Tensor, compute_dtype=torch.float32) -> Tensor:
+    def forward(self, x: Tensor, compute_dtype=torch.float32, *, hw: HW = None) -> Tensor:
         B, L, Cc = x.shape
-        H = W = int(math.sqrt(L))
+        H, W = block_hw(L, hw, "Upsample")
         y = ops.upsample(x.reshape(B * L, Cc), packing.pack_upsample(self.deconv[0].weight, compute_dtype),
                          self.deconv[0].bias.detach().float(), B, H, W)
         return y.reshape(B, 4 * L, self.out_channel)
@@ -226,9 +227,9 @@ class OutputProj(nn.Module):
         self.in_channel = in_channel
         self.out_channel = out_channel
 
-    def forward(self, x: Tensor, img: Optional[Tensor] = None) -> Tensor:
+    def forward(self, x: Tensor, img: Optional[Tensor] = None, *, hw: HW = None) -> Tensor:
         B, L, Cc = x.shape
-        H = W = int(math.sqrt(L))
+        H, W = block_hw(L, hw if hw is not None or img is None else tuple(img.shape[-2:]), "OutputProj")
         return ops.output_proj(x.reshape(B * L, Cc), packing.pack_output_proj(self.proj[0].weight),
                                self.proj[0].bias.detach().float(), B, H, W, img)
 
@@ -292,10 +293,10 @@ class LeWinTransformerBlock(nn.Module):
         am = mw.unsqueeze(2) * mw.unsqueeze(1)
         return torch.where(am != 0, torch.full_like(am, -100.0), torch.zeros_like(am)).contiguous()
 
-    def forward(self, x: Tensor, mask: Optional[Tensor] = None, compute_dtype=torch.float32) -> Tensor:
-        """(B, L, C) -> (B, L, C).  With grad mode on and something to differentiate (train() mode, an input or a parameter that
-        requires grad) the block is an autograd node like the reference's (model.py:908-989): op-by-op forward that keeps its
-        intermediates + the op-level backward (uformer_amd.train.LeWinBlockFunction), timm's DropPath per sample in train() mode.
+    def forward(self, x: Tensor, mask: Optional[Tensor] = None, compute_dtype=torch.float32, *, hw: HW = None) -> Tensor:
+        """(B, L, C) -> (B, L, C); ``hw`` = (H, W) of the map (None: the square side of L).  With grad mode on and something to
+        differentiate (train() mode, an input or a parameter that requires grad) the block is an autograd node like the reference's
+        (model.py:908-989): op-by-op forward that keeps its intermediates + the op-level backward (uformer_amd.train.LeWinBlockFunction), timm's DropPath per sample in train() mode.
         Otherwise: the fused inference kernels (DropPath is the identity)."""
         if torch.is_grad_enabled() and mask is None and (self.training or x.requires_grad or any(p.requires_grad for p in self.parameters())):
             from . import train
@@ -307,11 +308,13 @@ class LeWinTransformerBlock(nn.Module):
                 drop = getattr(self, "_drop_scales_override", None)
                 if drop is None:
                     drop = train.sample_drop_scales([self.drop_path_rate], x.shape[0], x.device)
-            return train.LeWinBlockFunction.apply(x, [n for n, _ in named], self.num_heads, self.shift_size, compute_dtype, drop, *[t for _, t in named])
+            hw = block_hw(x.shape[1], hw, "LeWinTransformerBlock")
+            return train.LeWinBlockFunction.apply(x, [n for n, _ in named], self.num_heads, self.shift_size, compute_dtype, drop, hw,
+                                                  *[t for _, t in named])
         if self.training and torch.is_grad_enabled():
             raise NotImplementedError("the mask argument is not supported by the block's autograd path (no reference script passes it)")
         B, L, Cc = x.shape
-        H = W = int(math.sqrt(L))
+        H, W = block_hw(L, hw, "LeWinTransformerBlock")
         if not x.is_cuda:
             raise UformerHipError("LeWinTransformerBlock runs on the GPU only; there is no CPU path")
         dt = ops.uf_dtype(compute_dtype)
@@ -348,9 +351,9 @@ class BasicUformerLayer(nn.Module):
                                   modulator=modulator, cross_modulator=cross_modulator)
             for i in range(depth)])
 
-    def forward(self, x, mask=None, compute_dtype=torch.float32):
+    def forward(self, x, mask=None, compute_dtype=torch.float32, *, hw: HW = None):
         for blk in self.blocks:
-            x = blk(x, None if self.use_checkpoint else mask, compute_dtype)  # checkpoint drops mask, model.py:1057
+            x = blk(x, None if self.use_checkpoint else mask, compute_dtype, hw=hw)  # checkpoint drops mask, model.py:1057
         return x
 
 
@@ -581,17 +584,19 @@ class Uformer(nn.Module):
         """Module-by-module path (used when the rarely-used ``mask`` argument is given):
         the same wiring as model.py:1269-1305, every step through the C ABI."""
         cd = self.compute_dtype
+        H, W = x.shape[-2:]
+        r = [(H // d, W // d) for d in (1, 2, 4, 8, 16)]     # (height, width) of each resolution level
         y = self.input_proj(x.detach().float())
-        conv0 = self.encoderlayer_0(y, mask, cd)
-        conv1 = self.encoderlayer_1(self.dowsample_0(conv0, cd), mask, cd)
-        conv2 = self.encoderlayer_2(self.dowsample_1(conv1, cd), mask, cd)
-        conv3 = self.encoderlayer_3(self.dowsample_2(conv2, cd), mask, cd)
-        conv4 = self.conv(self.dowsample_3(conv3, cd), mask, cd)
-        d0 = self.decoderlayer_0(torch.cat([self.upsample_0(conv4, cd), conv3], -1), mask, cd)
-        d1 = self.decoderlayer_1(torch.cat([self.upsample_1(d0, cd), conv2], -1), mask, cd)
-        d2 = self.decoderlayer_2(torch.cat([self.upsample_2(d1, cd), conv1], -1), mask, cd)
-        d3 = self.decoderlayer_3(torch.cat([self.upsample_3(d2, cd), conv0], -1), mask, cd)
-        out = self.output_proj(d3, x.detach().float() if self.dd_in == 3 else None)
+        conv0 = self.encoderlayer_0(y, mask, cd, hw=r[0])
+        conv1 = self.encoderlayer_1(self.dowsample_0(conv0, cd, hw=r[0]), mask, cd, hw=r[1])
+        conv2 = self.encoderlayer_2(self.dowsample_1(conv1, cd, hw=r[1]), mask, cd, hw=r[2])
+        conv3 = self.encoderlayer_3(self.dowsample_2(conv2, cd, hw=r[2]), mask, cd, hw=r[3])
+        conv4 = self.conv(self.dowsample_3(conv3, cd, hw=r[3]), mask, cd, hw=r[4])
+        d0 = self.decoderlayer_0(torch.cat([self.upsample_0(conv4, cd, hw=r[4]), conv3], -1), mask, cd, hw=r[3])
+        d1 = self.decoderlayer_1(torch.cat([self.upsample_1(d0, cd, hw=r[3]), conv2], -1), mask, cd, hw=r[2])
+        d2 = self.decoderlayer_2(torch.cat([self.upsample_2(d1, cd, hw=r[2]), conv1], -1), mask, cd, hw=r[1])
+        d3 = self.decoderlayer_3(torch.cat([self.upsample_3(d2, cd, hw=r[1]), conv0], -1), mask, cd, hw=r[0])
+        out = self.output_proj(d3, x.detach().float() if self.dd_in == 3 else None, hw=r[0])
         return out.to(x.dtype)
 
     def flops(self):

@@ -744,6 +744,32 @@ def crop_clamp(canvas: Tensor, h: int, w: int, clamp: bool = True) -> Tensor:
     return out
 
 
+def expand_canvas(img: Tensor, Xh: int, Xw: int, with_mask: bool = True):
+    """(B,C,h,w) -> zero canvas (B,C,Xh,Xw) with the image at ((Xh-h)//2, (Xw-w)//2) -- expand2square's placement rule on
+    each axis -- + the (B,1,Xh,Xw) mask of ones over the image (or None)."""
+    _dev(img)
+    img = _c(img, torch.float32)
+    B, Cc, h, w = img.shape
+    if Xh < h or Xw < w:
+        raise UformerHipError(f"expand_canvas: canvas {Xh}x{Xw} smaller than the image {h}x{w}")
+    canvas = torch.empty((B, Cc, Xh, Xw), dtype=torch.float32, device=img.device)
+    mask = torch.empty((B, 1, Xh, Xw), dtype=torch.float32, device=img.device) if with_mask else None
+    with torch.cuda.device(img.device):
+        _lib.check(_lib.load().uf_expand_canvas(_ptr(img), _ptr(canvas), _ptr(mask), B, Cc, h, w, Xh, Xw, _stream()), "uf_expand_canvas")
+    return canvas, mask
+
+
+def crop_clamp_canvas(canvas: Tensor, h: int, w: int, clamp: bool = True) -> Tensor:
+    """Inverse of expand_canvas: the (B,C,h,w) region at ((Xh-h)//2, (Xw-w)//2) of a (B,C,Xh,Xw) canvas, optionally clamped to [0,1]."""
+    _dev(canvas)
+    canvas = _c(canvas, torch.float32)
+    B, Cc, Xh, Xw = canvas.shape
+    out = torch.empty((B, Cc, h, w), dtype=torch.float32, device=canvas.device)
+    with torch.cuda.device(canvas.device):
+        _lib.check(_lib.load().uf_crop_clamp_canvas(_ptr(canvas), _ptr(out), B, Cc, h, w, Xh, Xw, int(clamp), _stream()), "uf_crop_clamp_canvas")
+    return out
+
+
 def crop_augment(frames: Tensor, meta: Tensor, ps: int, hwc: bool = False) -> Tensor:
     """frames: (N,3,H,W) or (N,H,W,3) (hwc) uint8 / f32 on the GPU; meta int32 (B,4) = [frame index, r0, c0, transform 0..7]
     -> (B,3,ps,ps) f32 patches (dataset/dataset_denoise.py:54-70; uint8 is divided by 255 like load_img)."""

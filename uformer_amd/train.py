@@ -161,13 +161,29 @@ class NativeBlockPack:
 # ------------------------------------------------------------------------------------------------------------------
 # LeWin block (model.py:908-989)
 # ------------------------------------------------------------------------------------------------------------------
+def block_hw(L: int, hw: Optional[Tuple[int, int]], who: str = "LeWin block") -> Tuple[int, int]:
+    """(H, W) of a (B, L, C) token map: ``hw`` when given (checked against L), else the square side the reference takes
+    (model.py:910-911).  A non-square L without ``hw`` is an error, not a guess."""
+    if hw is not None:
+        H, W = int(hw[0]), int(hw[1])
+        if H * W != L:
+            raise ops.UformerHipError(f"{who}: hw={H}x{W} does not match L={L} tokens")
+        return H, W
+    r = math.isqrt(L)
+    if r * r != L:
+        raise ops.UformerHipError(f"{who}: L={L} tokens is not a square map; pass hw=(H, W) for a rectangular one")
+    return r, r
+
+
 def lewin_block_forward(x: Tensor, p: Dict[str, Tensor], prefix: str, heads: int, shift: int, dtype: torch.dtype,
-                        drop: Optional[Tensor] = None, pk: Optional[BlockPack] = None, need_y: bool = True) -> Tuple[Optional[Tensor], Saved]:
+                        drop: Optional[Tensor] = None, pk: Optional[BlockPack] = None, need_y: bool = True,
+                        hw: Optional[Tuple[int, int]] = None) -> Tuple[Optional[Tensor], Saved]:
     """x: (B, L, C) f32 on the GPU -> (y, saved).  Op-by-op forward that keeps what the backward reads (also the RECOMPUTATION a
     block runs at the start of its backward).  ``drop``: None (eval) or (2, B) per-sample DropPath scales bernoulli(keep)/keep of
-    the two residual branches (model.py:986-987).  ``need_y=False``: the recomputation stops before linear2 (nothing reads y)."""
+    the two residual branches (model.py:986-987).  ``need_y=False``: the recomputation stops before linear2 (nothing reads y).
+    ``hw``: the (H, W) of the map (needed when H != W; default: the square side of L)."""
     B, L, C = x.shape
-    H = W = int(math.sqrt(L))
+    H, W = block_hw(L, hw)
     M = B * L
     T = dtype
     pk = pk or BlockPack(p, prefix, heads, shift, T, fused=fused_attn_covers(T, C, heads))
@@ -200,7 +216,7 @@ def lewin_block_forward(x: Tensor, p: Dict[str, Tensor], prefix: str, heads: int
     y = None
     if need_y:
         y = ops.linear_residual(g2, pk.w2, f("mlp.linear2.0.bias"), x1, s2, B, H, W).reshape(B, L, C)     # x1 + DropPath(linear2(.))   model.py:987
-    saved = dict(s1=s1, s2=s2, p=p, prefix=prefix, heads=heads, shift=shift, T=T, shape=(B, L, C), x2=x2, xn=xn, q=q, k=k, vt=vt, o=o, x1=x1, z=z, a1=a1,
+    saved = dict(s1=s1, s2=s2, p=p, prefix=prefix, heads=heads, shift=shift, T=T, shape=(B, L, C), hw=(H, W), x2=x2, xn=xn, q=q, k=k, vt=vt, o=o, x1=x1, z=z, a1=a1,
                  h1=h1, c=c, g2=g2, pk=pk, mod=pk.mod is not None)
     return y, saved
 
@@ -264,7 +280,7 @@ def lewin_block_backward(sv: Saved, dy: Tensor, dyT: Optional[Tensor] = None, ne
     p, prefix, heads, shift, T = sv["p"], sv["prefix"], sv["heads"], sv["shift"], sv["T"]
     side = _Side(dy.device)
     B, L, C = sv["shape"]
-    H = W = int(math.sqrt(L))
+    H, W = sv["hw"] if "hw" in sv else block_hw(L, None)
     M, hd = B * L, C // heads
     f = lambda k: p[prefix + k]                                             # noqa: E731
     g: Grads = {}
@@ -389,19 +405,20 @@ def _conv3x3_backward(x: Tensor, nchw: bool, geom: Tuple[int, int, int, int], w:
 _RECOMPUTE_CHOICE: Dict[tuple, bool] = {}
 
 
-def choose_recompute(cfg, B: int, H: int, device) -> bool:
+def choose_recompute(cfg, B: int, H: int, device, W: Optional[int] = None) -> bool:
     """Kept-intermediates or recompute form for (arch, batch, resolution) on this device -- decided ONCE and remembered, so every step of a run (and,
     under DDP, every rank: the choice is reduced with MAX over the process group) takes the same kernels and rounds the same way (the
     per-forward decision compared against the driver's free memory, which excludes what PyTorch's caching allocator reserved on the previous step,
     and could flip between steps or differ between ranks).  The memory that counts as available = the driver's free bytes + the allocator's
-    reserved-but-unallocated bytes."""
+    reserved-but-unallocated bytes.  ``W`` (default: ``H``): the width of a rectangular input."""
     dev_ = torch.device(device)
-    key = (tuple(cfg.depths), cfg.embed_dim, B, H, dev_.index if dev_.index is not None else torch.cuda.current_device())   # a bare "cuda" names the current device
+    W = H if W is None else W
+    key = (tuple(cfg.depths), cfg.embed_dim, B, H, W, dev_.index if dev_.index is not None else torch.cuda.current_device())   # a bare "cuda" names the current device
     # (Under DDP every rank must reach this point with the same (arch, batch, resolution) the first time: the choice is reduced over the process group.)
     if key not in _RECOMPUTE_CHOICE:
         dims, div = cfg.stage_dims(), cfg.stage_res_div()
         per_tc = 52 if _GELU_IN else 60           # bytes per token x channel of a block (measured 49.0 / 56.5 GB for Uformer-B 256^2 at batch 32); round 4: linear1's activation is not kept
-        need = per_tc * B * sum(cfg.depths[s] * (H // div[s]) ** 2 * dims[s] for s in range(9))
+        need = per_tc * B * sum(cfg.depths[s] * (H // div[s]) * (W // div[s]) * dims[s] for s in range(9))
         free = torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
         choice = need > min(0.5 * free, 96e9)      # past ~100 GB the two forms measure the same (batch 64: 356 vs 357 img/s): keep the small one
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
@@ -410,7 +427,7 @@ def choose_recompute(cfg, B: int, H: int, device) -> bool:
             choice = bool(flag.item() > 0)
         _RECOMPUTE_CHOICE[key] = choice
         if _VERBOSE:
-            print(f"[uformer_amd.train] batch {B} at {H}x{H}: {'recompute' if choice else 'kept-intermediates'} form ({need / 1e9:.1f} GB of intermediates, {free / 1e9:.1f} GB available)", flush=True)
+            print(f"[uformer_amd.train] batch {B} at {H}x{W}: {'recompute' if choice else 'kept-intermediates'} form ({need / 1e9:.1f} GB of intermediates, {free / 1e9:.1f} GB available)", flush=True)
     return _RECOMPUTE_CHOICE[key]
 
 
@@ -433,12 +450,12 @@ class UformerTape:
         from .spec import STAGES
         sd, cfg, T = self.sd, self.cfg, self.T
         B, _, H, W = img.shape
-        self.B, self.H = B, H
+        self.B, self.H, self.W = B, H, W
         if self.recompute is None:
             # Keeping every intermediate of the op-by-op forward costs ~52 bytes per token x channel of every block (measured: 49 GB for
             # Uformer-B 256^2 at batch 32 against 17 GB) and saves the recomputation in the backward: 371 vs 334 img/s on an MI355X
             # (profiles/r03_host.txt).  288 GB of HBM is there to be used: keep them while that is under half of the free memory.
-            self.recompute = choose_recompute(cfg, B, H, img.device)
+            self.recompute = choose_recompute(cfg, B, H, img.device, W)
         # widths the training kernels cover, checked once with a clear message (they used to fail deep inside the tape with UF_ERR_SHAPE)
         dims_ = cfg.stage_dims()
         for s_ in range(9):
@@ -451,7 +468,8 @@ class UformerTape:
             warnings.warn("the recompute form was selected (use_checkpoint=True, recompute=True, or chosen from the free memory), but no stage has head_dim 32 (the fused kernels the recompute form is built on): every block keeps its "
                           "intermediates (memory ~18x the recompute form)", stacklevel=2)
         shifts = cfg.block_shifts()
-        res = self.res = [H, H // 2, H // 4, H // 8, H // 16, H // 8, H // 4, H // 2, H]
+        div = cfg.stage_res_div()
+        res = self.res = [(H // div[s], W // div[s]) for s in range(9)]      # (height, width) per stage
         first = [sum(cfg.depths[:s]) for s in range(9)]
         self.saved_blocks: List[List[Saved]] = [[] for _ in range(9)]
         self.packs: Dict[str, BlockPack] = {}
@@ -472,11 +490,11 @@ class UformerTape:
                 pk = self.packs[prefix] = (NativeBlockPack(sd, prefix, cfg.num_heads[s], shifts[s][i], T) if native else
                                            BlockPack(sd, prefix, cfg.num_heads[s], shifts[s][i], T, fused=fusable or fused_attn_covers(T, C, cfg.num_heads[s])))
                 if fusable:                                                     # fused kernels; the block's input is all that is kept
-                    y = ops.lewin_block_train_fwd(pk.fused, t, B, res[s], res[s], T, None if dr is None else dr[0], None if dr is None else dr[1])
+                    y = ops.lewin_block_train_fwd(pk.fused, t, B, res[s][0], res[s][1], T, None if dr is None else dr[0], None if dr is None else dr[1])
                     self.saved_blocks[s].append(dict(x=t, drop=dr, pk=pk))
                     t = y
                 else:
-                    y, sv = lewin_block_forward(t.reshape(B, res[s] * res[s], C), sd, prefix, cfg.num_heads[s], shifts[s][i], T, dr, pk)
+                    y, sv = lewin_block_forward(t.reshape(B, res[s][0] * res[s][1], C), sd, prefix, cfg.num_heads[s], shifts[s][i], T, dr, pk, hw=res[s])
                     self.saved_blocks[s].append(sv)
                     t = y.reshape(-1, C)
             return t
@@ -492,7 +510,7 @@ class UformerTape:
             self.down_in.append(t)
             wd = packing.pack_downsample(sd[f"dowsample_{s}.conv.0.weight"], T)
             wd_fm = ops.pack_weight_fm(wd) if (T in (torch.bfloat16, torch.float16) and wd.shape[0] % 16 == 0 and wd.shape[1] % 32 == 0) else None     # the LDS-patch form streams it (round 6)
-            t = ops.downsample(t, wd, sd[f"dowsample_{s}.conv.0.bias"], B, res[s], res[s], w_fm=wd_fm)
+            t = ops.downsample(t, wd, sd[f"dowsample_{s}.conv.0.bias"], B, res[s][0], res[s][1], w_fm=wd_fm)
         t = stage_fwd(4, t)
         for k in range(4):
             self.up_in.append(t)
@@ -501,7 +519,7 @@ class UformerTape:
             skip = self.skips[3 - k]
             Cs = skip.shape[1]
             cat = torch.empty((skip.shape[0], 2 * Cs), dtype=torch.float32, device=skip.device)
-            ops.upsample(t, packing.pack_upsample(sd[f"upsample_{k}.deconv.0.weight"], T), sd[f"upsample_{k}.deconv.0.bias"], B, res[4 + k], res[4 + k],
+            ops.upsample(t, packing.pack_upsample(sd[f"upsample_{k}.deconv.0.weight"], T), sd[f"upsample_{k}.deconv.0.bias"], B, res[4 + k][0], res[4 + k][1],
                          out=cat, ld_o=2 * Cs)
             cat[:, Cs:].copy_(skip)
             t = stage_fwd(5 + k, cat)
@@ -512,13 +530,13 @@ class UformerTape:
     def _block_ws(self, s: int) -> Tensor:
         """one workspace for every block backward of the sweep (sized for the largest stage)"""
         if getattr(self, "_bws", None) is None:
-            need = max(ops.lewin_block_bwd_workspace_bytes(self.B, r, r, self.stage_C[i], self.cfg.num_heads[i], self.T) for i, r in enumerate(self.res))
+            need = max(ops.lewin_block_bwd_workspace_bytes(self.B, rh, rw, self.stage_C[i], self.cfg.num_heads[i], self.T) for i, (rh, rw) in enumerate(self.res))
             self._bws = torch.empty(need, dtype=torch.uint8, device=self.img.device)
         return self._bws
 
     def backward(self, dy: Tensor, need_dimg: bool = True) -> Tuple[Optional[Tensor], Grads]:
         from .spec import STAGES
-        sd, cfg, T, B, H, res = self.sd, self.cfg, self.T, self.B, self.H, self.res
+        sd, cfg, T, B, H, W, res = self.sd, self.cfg, self.T, self.B, self.H, self.W, self.res
         g: Grads = {}
 
         def done(names):
@@ -527,7 +545,7 @@ class UformerTape:
 
         def stage_bwd(s: int, d: Tensor, g: Grads) -> Tensor:
             C = d.shape[1]
-            d = d.reshape(B, res[s] * res[s], C)
+            d = d.reshape(B, res[s][0] * res[s][1], C)
             names = []
             blocks = self.saved_blocks[s]
             dyT = None                                                            # T(d * s2 of the block about to run): from the previous block's LN1 backward
@@ -536,8 +554,8 @@ class UformerTape:
                 if "x2" not in sv:                                                # only the block input was kept: recomputation + backward in one C call
                     pk, dr = sv["pk"], sv["drop"]
                     dxb, gv = ops.lewin_block_bwd(pk.train_params, sv["x"], d.reshape(-1, C), None if dr is None else dr[0], None if dr is None else dr[1],
-                                                  B, res[s], res[s], pk.heads, T, ws=self._block_ws(s))
-                    d, gb = dxb.reshape(B, res[s] * res[s], C), _named_block_grads(pk.prefix, gv, C)
+                                                  B, res[s][0], res[s][1], pk.heads, T, ws=self._block_ws(s))
+                    d, gb = dxb.reshape(B, res[s][0] * res[s][1], C), _named_block_grads(pk.prefix, gv, C)
                 elif blocks and "x2" in blocks[-1]:                               # the block that ran before this one reads T(d * its s2): made here
                     d, gb, dyT = lewin_block_backward(sv, d, dyT, next_scale=blocks[-1]["s2"])
                 else:
@@ -550,9 +568,9 @@ class UformerTape:
             return d.reshape(-1, C)
 
         dy = dy.float()
-        dy_rows = dy.permute(0, 2, 3, 1).reshape(B * H * H, 3)
+        dy_rows = dy.permute(0, 2, 3, 1).reshape(B * H * W, 3)
         C8 = self.head_in.shape[1]
-        d, g["output_proj.proj.0.weight"], g["output_proj.proj.0.bias"] = _conv3x3_backward(self.head_in, False, (B, H, H, C8), sd["output_proj.proj.0.weight"], dy_rows, T)
+        d, g["output_proj.proj.0.weight"], g["output_proj.proj.0.bias"] = _conv3x3_backward(self.head_in, False, (B, H, W, C8), sd["output_proj.proj.0.weight"], dy_rows, T)
         done(["output_proj.proj.0.weight", "output_proj.proj.0.bias"])
         self.head_in = None
         dskip: List[Tensor] = [None] * 4
@@ -562,10 +580,10 @@ class UformerTape:
             cup = d.shape[1] - Cs
             dskip[3 - k] = d[:, cup:].contiguous()
             # ConvTranspose2d k2 s2 = four independent 1x1 GEMMs over the 2x2 output pixels of every input pixel (uf_upsample_cat_bwd)
-            r = res[4 + k]
+            rh, rw = res[4 + k]
             w = sd[f"upsample_{k}.deconv.0.weight"]                                # (Cin, Cout, 2, 2)
             wpk_t = packing.pack_upsample(w, T).t().contiguous()                   # (Cin, 4*Cout), n = (dy*2+dx)*Cout + co
-            d, dWp, g[f"upsample_{k}.deconv.0.bias"] = ops.upsample_cat_bwd(d, self.up_in[k], wpk_t, B, r, r)
+            d, dWp, g[f"upsample_{k}.deconv.0.bias"] = ops.upsample_cat_bwd(d, self.up_in[k], wpk_t, B, rh, rw)
             g[f"upsample_{k}.deconv.0.weight"] = dWp.reshape(2, 2, cup, w.shape[0]).permute(3, 2, 0, 1).contiguous()
             done([f"upsample_{k}.deconv.0.weight", f"upsample_{k}.deconv.0.bias"])
             self.up_in[k] = None
@@ -573,14 +591,14 @@ class UformerTape:
         for s in reversed(range(4)):
             Cs = self.down_in[s].shape[1]
             wd = sd[f"dowsample_{s}.conv.0.weight"]                                  # (2C, C, 4, 4)
-            dx, dWp, g[f"dowsample_{s}.conv.0.bias"] = ops.downsample_bwd(self.down_in[s], d, packing.pack_downsample(wd, T).t().contiguous(), B, res[s], res[s],
+            dx, dWp, g[f"dowsample_{s}.conv.0.bias"] = ops.downsample_bwd(self.down_in[s], d, packing.pack_downsample(wd, T).t().contiguous(), B, res[s][0], res[s][1],
                                                                          add_to=dskip[s])
             g[f"dowsample_{s}.conv.0.weight"] = dWp.reshape(wd.shape[0], 4, 4, Cs).permute(0, 3, 1, 2).contiguous()
             done([f"dowsample_{s}.conv.0.weight", f"dowsample_{s}.conv.0.bias"])
             self.down_in[s] = self.skips[s] = None
             d = stage_bwd(s, dx, g)
         # InputProj: LeakyReLU(0.01)' (model.py:786) from the sign of the stored output, folded into the conv backward
-        dimg, g["input_proj.proj.0.weight"], g["input_proj.proj.0.bias"] = _conv3x3_backward(self.img.float(), True, (B, H, H, self.img.shape[1]), sd["input_proj.proj.0.weight"], d, T,
+        dimg, g["input_proj.proj.0.weight"], g["input_proj.proj.0.bias"] = _conv3x3_backward(self.img.float(), True, (B, H, W, self.img.shape[1]), sd["input_proj.proj.0.weight"], d, T,
                                                                                              act_out=self.stem_out, need_dx=need_dimg)
         done(["input_proj.proj.0.weight", "input_proj.proj.0.bias"])
         if need_dimg and cfg.dd_in == 3:
@@ -635,14 +653,15 @@ class UformerFunction(torch.autograd.Function):
 
 class LeWinBlockFunction(torch.autograd.Function):
     """torch.autograd entry of ONE LeWin block (the reference's LeWinTransformerBlock is an ordinary differentiable module,
-    model.py:908-989): ``y = LeWinBlockFunction.apply(x, prefix_free_names, heads, shift, dtype, drop, *params)`` with x (B, L, C).
+    model.py:908-989): ``y = LeWinBlockFunction.apply(x, prefix_free_names, heads, shift, dtype, drop, hw, *params)`` with x (B, L, C) and
+    ``hw`` = (H, W) of the map (None: the square side of L).
     Forward = the op-by-op forward that keeps its intermediates, backward = the op-level backward (lewin_block_forward /
     lewin_block_backward above); ``drop``: None or (2, B) DropPath scales of the two residual branches."""
 
     @staticmethod
-    def forward(ctx, x, names, heads, shift, dtype, drop, *params):
+    def forward(ctx, x, names, heads, shift, dtype, drop, hw, *params):
         p = {n: t.detach() for n, t in zip(names, params)}
-        y, sv = lewin_block_forward(x.detach().float().contiguous(), p, "", heads, shift, dtype, drop)
+        y, sv = lewin_block_forward(x.detach().float().contiguous(), p, "", heads, shift, dtype, drop, hw=hw)
         ctx.sv, ctx.names, ctx.x_needs_grad, ctx.x_dtype = sv, names, x.requires_grad, x.dtype
         return y.to(x.dtype)
 
@@ -650,7 +669,7 @@ class LeWinBlockFunction(torch.autograd.Function):
     def backward(ctx, dy):
         dx, g = lewin_block_backward(ctx.sv, dy.float().contiguous())
         ctx.sv = None
-        return (dx.to(ctx.x_dtype) if ctx.x_needs_grad else None, None, None, None, None, None) + tuple(g.get(n) for n in ctx.names)
+        return (dx.to(ctx.x_dtype) if ctx.x_needs_grad else None, None, None, None, None, None, None) + tuple(g.get(n) for n in ctx.names)
 
 
 class NamesWithSink(list):
