@@ -528,6 +528,53 @@ size_t uf_uformer_workspace_bytes(const uf_model_desc* d, int B, int H, int W, u
 int uf_uformer_fwd(const uf_model_desc* d, const float* img, float* out, int B, int H, int W,
                    uf_dtype dtype, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * 4x4-window blocks.  A Uformer built for 64x64 patches (img_size 64, get_arch(opt) with --train_ps 64) has a bottleneck of
+ * resolution 4: LeWinTransformerBlock clamps its window to 4 and its shift to 0 (model.py:863-866), so its two blocks carry a
+ * (49, heads) relative_position_bias_table and a (16, 16) index.  These entry points run such blocks.  The window geometry lives
+ * in the kernels' addressing: q|k|v, the attention output and the gradients are RASTER token rows (B*H*W, .) of a (B, H, W) map,
+ * H and W multiples of 4; window w = image-major, then row-major over the (H/4, W/4) windows (window_partition's order).
+ * head_dim 16 or 32; operand type T = f32, bf16 or f16; scores, softmax and products accumulate in f32.
+ * ------------------------------------------------------------------------------------------------------------------------- */
+typedef struct uf_block4_params {
+    const float* norm1_w;  const float* norm1_b;  const float* norm2_w;  const float* norm2_b;   /* (C) each */
+    const float* rpb4;      /* (heads, 49) f32: T4[h][(dy+3)*7 + dx+3] = bias of a query / key pair at (dy, dx) = (yq-yk, xq-xk);
+                             * = relative_position_bias_table (49, heads) transposed for the reference's relative_position_index */
+    const void* wqkv;       /* T (3C,C) row-major: cat(attn.qkv.to_q.weight, attn.qkv.to_kv.weight) */
+    const float* bqkv;      /* (3C) */
+    const void* wproj;  const float* bproj;    /* T (C,C), (C) */
+    const void* w1;     const float* b1;       /* T (4C,C), (4C) */
+    const float* wdw9;  const float* bdw;      /* (9,4C) tap-major mlp.dwconv.0.weight, (4C) */
+    const void* w2;     const float* b2;       /* T (C,4C), (C) */
+    int32_t heads;          /* no modulator: the reference's (64, C) embedding does not broadcast onto 16-token windows */
+} uf_block4_params;
+
+/* qkv: T rows (B*H*W, ld_qkv), q | k | v in columns [0,C) [C,2C) [2C,3C) (the unscaled projection outputs; the kernel applies
+ * head_dim^-0.5).  o: T rows (B*H*W, ld_o) = softmax(q k^T * scale + bias) v per 4x4 window and head, heads merged. */
+int uf_window4_attention_fwd(const void* qkv, int ld_qkv, const float* rpb4, void* o, int ld_o, int B, int H, int W, int C, int heads,
+                             uf_dtype dtype, void* stream);
+/* Backward of uf_window4_attention_fwd from dout (T rows, ld_do): dqkv T rows (B*H*W, ld_dqkv), the gradient of the q|k|v
+ * projection outputs (dq includes the query scale); dscore f32 (n_windows, heads, 16, 16) = d loss / d score per window, the
+ * input of uf_rpb4_table_grad.  n_windows = B * (H/4) * (W/4). */
+int uf_window4_attention_bwd(const void* qkv, int ld_qkv, const float* rpb4, const void* dout, int ld_do, void* dqkv, int ld_dqkv,
+                             float* dscore, int B, int H, int W, int C, int heads, uf_dtype dtype, void* stream);
+/* dtable (49, heads) f32 = the relative_position_bias_table gradient: dscore summed over the windows and gathered over the pairs of
+ * each table entry, in a fixed order (deterministic, no atomics). */
+int uf_rpb4_table_grad(const float* dscore, float* dtable, int n_windows, int heads, void* stream);
+/* window_partition / window_reverse at win 4 (model.py:704-726): (B,H,W,C) <-> (B*nW,4,4,C), elements of 2 or 4 bytes. */
+int uf_window4_partition(const void* x, void* out, int B, int H, int W, int C, int elem_bytes, void* stream);
+int uf_window4_reverse(const void* windows, void* out, int B, int H, int W, int C, int elem_bytes, void* stream);
+/* One 4x4-window LeWin block, in place on f32 rows x (B*H*W, ld): LN1, q|k|v, window attention, proj + residual, LN2, linear1 + GELU,
+ * depthwise 3x3 + GELU, linear2 + residual (model.py:908-989).  drop_attn / drop_leff: per-image DropPath scales (B) or NULL.
+ * Workspace: uf_block_workspace_bytes(B*H*W, C, dtype) bytes, 256-byte aligned. */
+int uf_lewin_block4_fwd(const uf_block4_params* p, float* x, int ld, int B, int H, int W, int C, const float* drop_attn,
+                        const float* drop_leff, uf_dtype dtype, void* ws, size_t ws_bytes, void* stream);
+/* Whole forward of a model built for 64x64 patches: uf_uformer_fwd with the bottleneck's depths[4] blocks run from `bottleneck`
+ * (their d->blocks entries are skipped).  H and W each a positive multiple of 64 (4 downsamplings x window 4). */
+size_t uf_uformer_win4_workspace_bytes(const uf_model_desc* d, int B, int H, int W, uf_dtype dtype);
+int uf_uformer_win4_fwd(const uf_model_desc* d, const uf_block4_params* bottleneck, const float* img, float* out, int B, int H, int W,
+                        uf_dtype dtype, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

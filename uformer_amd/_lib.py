@@ -46,6 +46,13 @@ class BlockGrads(C.Structure):
         "norm1_w", "norm1_b", "norm2_w", "norm2_b", "modulator", "rpb_table", "wqkv", "bqkv", "wproj", "bproj", "w1", "b1", "wdw", "bdw", "w2", "b2")]
 
 
+class Block4Params(C.Structure):
+    """``uf_block4_params`` (include/uformer_hip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "norm1_w", "norm1_b", "norm2_w", "norm2_b", "rpb4", "wqkv", "bqkv", "wproj", "bproj", "w1", "b1", "wdw9", "bdw", "w2", "b2")] + [
+        ("heads", C.c_int32)]
+
+
 class ModelDesc(C.Structure):
     """``uf_model_desc`` (include/uformer_hip.h)."""
     _fields_ = [
@@ -151,6 +158,14 @@ SIGNATURES = {
     "uf_mixup": (I, [P, P, P, P, I, C.c_longlong, P]),
     "uf_uformer_workspace_bytes": (c_size_t, [C.POINTER(ModelDesc), I, I, I, I]),
     "uf_uformer_fwd": (I, [C.POINTER(ModelDesc), P, P, I, I, I, I, P, c_size_t, P]),
+    "uf_window4_attention_fwd": (I, [P, I, P, P, I, I, I, I, I, I, I, P]),
+    "uf_window4_attention_bwd": (I, [P, I, P, P, I, P, I, P, I, I, I, I, I, I, P]),
+    "uf_rpb4_table_grad": (I, [P, P, I, I, P]),
+    "uf_window4_partition": (I, [P, P, I, I, I, I, I, P]),
+    "uf_window4_reverse": (I, [P, P, I, I, I, I, I, P]),
+    "uf_lewin_block4_fwd": (I, [C.POINTER(Block4Params), P, I, I, I, I, I, P, P, I, P, c_size_t, P]),
+    "uf_uformer_win4_workspace_bytes": (c_size_t, [C.POINTER(ModelDesc), I, I, I, I]),
+    "uf_uformer_win4_fwd": (I, [C.POINTER(ModelDesc), C.POINTER(Block4Params), P, P, I, I, I, I, P, c_size_t, P]),
 }
 
 _lock = threading.Lock()

@@ -223,10 +223,12 @@ struct Plan {
     size_t total;
 };
 
-int make_plan(Plan& pl, const uf_model_desc* d, int B, int H, int W, uf_dtype dtype) {
+// bwin: the bottleneck's window (8, or 4 for a model built for 64x64 patches: uf_uformer_win4_fwd); the other stages' is 8
+int make_plan(Plan& pl, const uf_model_desc* d, int B, int H, int W, uf_dtype dtype, int bwin = 8) {
     UF_REQUIRE(d, UF_ERR_NULL, "model desc is null");
-    UF_REQUIRE(H % 128 == 0 && H > 0, UF_ERR_SHAPE, "H=%d must be a positive multiple of 128 (4 downsamplings x window 8)", H);
-    UF_REQUIRE(W % 128 == 0 && W > 0, UF_ERR_SHAPE, "W=%d must be a positive multiple of 128 (4 downsamplings x window 8)", W);
+    const int unit = 16 * bwin;
+    UF_REQUIRE(H % unit == 0 && H > 0, UF_ERR_SHAPE, "H=%d must be a positive multiple of %d (4 downsamplings x window %d)", H, unit, bwin);
+    UF_REQUIRE(W % unit == 0 && W > 0, UF_ERR_SHAPE, "W=%d must be a positive multiple of %d (4 downsamplings x window %d)", W, unit, bwin);
     UF_REQUIRE(B > 0, UF_ERR_SHAPE, "B=%d", B);
     UF_REQUIRE(d->embed_dim >= 16 && d->embed_dim % 16 == 0, UF_ERR_SHAPE, "embed_dim=%d must be a multiple of 16", d->embed_dim);
     const int e = d->embed_dim;
@@ -264,11 +266,13 @@ extern "C" size_t uf_uformer_workspace_bytes(const uf_model_desc* d, int B, int 
     return pl.total + WS_SPLIT_SLACK;
 }
 
+// bneck (NULL for the standard model): the uf_block4_params of the bottleneck's depths[4] blocks, which then run on the 4x4-window path
+// (their uf_block_params entries in d->blocks are skipped)
 namespace {
-int forward_one_stream(const uf_model_desc* d, const float* img, float* out, int B, int H, int W, uf_dtype dtype,
+int forward_one_stream(const uf_model_desc* d, const uf_block4_params* bneck, const float* img, float* out, int B, int H, int W, uf_dtype dtype,
                        void* ws, size_t ws_bytes, void* stream) {
     Plan pl;
-    int rc = make_plan(pl, d, B, H, W, dtype);
+    int rc = make_plan(pl, d, B, H, W, dtype, bneck ? 4 : 8);
     if (rc) return rc;
     UF_REQUIRE(img && out && ws && d->blocks, UF_ERR_NULL, "uf_uformer_fwd: null pointer");
     UF_REQUIRE(((uintptr_t)ws % 256) == 0, UF_ERR_ALIGN, "uf_uformer_fwd: workspace must be 256-byte aligned");
@@ -292,7 +296,8 @@ int forward_one_stream(const uf_model_desc* d, const float* img, float* out, int
     // in round 3 -- profiles/r03_chunk_ab.txt -- and is gone.)
     auto run_stage = [&](int s, float* x, int ld) -> int {
         for (int i = 0; i < d->depths[s]; ++i, ++blk) {
-            int r = uf_lewin_block_fwd(blk, x, ld, B, pl.res_h[s], pl.res_w[s], pl.C[s], nullptr, 0, dtype, bws, pl.blk_bytes, st);
+            int r = (s == 4 && bneck) ? uf_lewin_block4_fwd(bneck + i, x, ld, B, pl.res_h[s], pl.res_w[s], pl.C[s], nullptr, nullptr, dtype, bws, pl.blk_bytes, st)
+                                      : uf_lewin_block_fwd(blk, x, ld, B, pl.res_h[s], pl.res_w[s], pl.C[s], nullptr, 0, dtype, bws, pl.blk_bytes, st);
             if (r) return r;
         }
         return UF_OK;
@@ -334,12 +339,13 @@ int forward_one_stream(const uf_model_desc* d, const float* img, float* out, int
 // Measured on one box, Uformer-B 256x256 B=16: 1 stream 2085 img/s, 2: 2135, 3: 2145, 4: 2100, 8: 1235 (host launch
 // bound).  Results are bit-identical to the one-stream run (every kernel is batch-size invariant,
 // tests/test_gpu_model.py); the caller's stream is ordered after all parts before the call returns.
-extern "C" int uf_uformer_fwd(const uf_model_desc* d, const float* img, float* out, int B, int H, int W, uf_dtype dtype,
-                              void* ws, size_t ws_bytes, void* stream) {
+namespace {
+int forward_split(const uf_model_desc* d, const uf_block4_params* bneck, const float* img, float* out, int B, int H, int W, uf_dtype dtype,
+                  void* ws, size_t ws_bytes, void* stream) {
     static const int env_streams = getenv("UF_STREAMS") ? atoi(getenv("UF_STREAMS")) : 0;
     int n = env_streams > 0 ? (env_streams > MAX_SIDE + 1 ? MAX_SIDE + 1 : env_streams) : (B >= 8 ? 2 : 1);
     if (n > B) n = B;
-    if (n < 2 || timing_enabled()) return forward_one_stream(d, img, out, B, H, W, dtype, ws, ws_bytes, stream);
+    if (n < 2 || timing_enabled()) return forward_one_stream(d, bneck, img, out, B, H, W, dtype, ws, ws_bytes, stream);
     UF_REQUIRE(d && img && out && ws, UF_ERR_NULL, "uf_uformer_fwd: null pointer");
     int dev = 0;
     Lane* ss = acquire_lane(n - 1, &dev);
@@ -352,12 +358,12 @@ extern "C" int uf_uformer_fwd(const uf_model_desc* d, const float* img, float* o
     for (int i = 0; i < n; ++i) {   // part i: images [b0, b0 + Bi); part 0 runs on the caller's stream
         const int Bi = B / n + (i < B % n ? 1 : 0);
         Plan pl;
-        int rc = make_plan(pl, d, Bi, H, W, dtype);
+        int rc = make_plan(pl, d, Bi, H, W, dtype, bneck ? 4 : 8);
         if (rc) return rc;
         UF_REQUIRE(ws_bytes >= off + pl.total, UF_ERR_WORKSPACE, "uf_uformer_fwd: workspace too small for %d streams", n);
         hipStream_t si = i == 0 ? st : ss->s[i - 1];
         if (i > 0) hipStreamWaitEvent(si, ss->fork, 0);
-        rc = forward_one_stream(d, img + (size_t)b0 * d->dd_in * H * W, out + (size_t)b0 * 3 * H * W, Bi, H, W, dtype, (char*)ws + off,
+        rc = forward_one_stream(d, bneck, img + (size_t)b0 * d->dd_in * H * W, out + (size_t)b0 * 3 * H * W, Bi, H, W, dtype, (char*)ws + off,
                                 pl.total, si);
         if (rc && !rc_all) rc_all = rc;
         if (i > 0) {
@@ -368,4 +374,23 @@ extern "C" int uf_uformer_fwd(const uf_model_desc* d, const float* img, float* o
         b0 += Bi;
     }
     return rc_all;
+}
+}  // namespace
+
+extern "C" int uf_uformer_fwd(const uf_model_desc* d, const float* img, float* out, int B, int H, int W, uf_dtype dtype,
+                              void* ws, size_t ws_bytes, void* stream) {
+    return forward_split(d, nullptr, img, out, B, H, W, dtype, ws, ws_bytes, stream);
+}
+
+// A model built for 64x64 patches (img_size 64): the same forward with the bottleneck on 4x4 windows; H and W multiples of 64.
+extern "C" size_t uf_uformer_win4_workspace_bytes(const uf_model_desc* d, int B, int H, int W, uf_dtype dtype) {
+    Plan pl;
+    if (make_plan(pl, d, B, H, W, dtype, 4) != UF_OK) return 0;
+    return pl.total + WS_SPLIT_SLACK;
+}
+
+extern "C" int uf_uformer_win4_fwd(const uf_model_desc* d, const uf_block4_params* bottleneck, const float* img, float* out, int B, int H, int W,
+                                   uf_dtype dtype, void* ws, size_t ws_bytes, void* stream) {
+    UF_REQUIRE(bottleneck, UF_ERR_NULL, "uf_uformer_win4_fwd: null bottleneck parameters");
+    return forward_split(d, bottleneck, img, out, B, H, W, dtype, ws, ws_bytes, stream);
 }

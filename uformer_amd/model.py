@@ -96,10 +96,23 @@ class WindowAttention(nn.Module):
 
     def forward(self, x: Tensor, attn_kv=None, mask: Optional[Tensor] = None, *, H: Optional[int] = None,
                 W: Optional[int] = None, shift: int = 0, compute_dtype=torch.float32) -> Tensor:
-        """x: (B_, 64, C) window tokens.  ``mask`` (nW,64,64) additive, as in model.py:508-512."""
+        """x: (B_, 64, C) window tokens (B_, 16, C at win_size 4).  ``mask`` (nW,64,64) additive, as in model.py:508-512."""
         if attn_kv is not None:
             raise NotImplementedError("attn_kv (cross-modulator) is out of scope: never enabled by get_arch")
         B_, N, Cc = x.shape
+        if self.win_size == (4, 4):
+            if mask is not None or shift:
+                raise NotImplementedError("4x4-window attention takes no mask and no shift (the reference clamps the shift to 0, model.py:863-866)")
+            if N != 16:
+                raise UformerHipError("4x4-window attention needs 16 tokens per window")
+            a = _to_compute(x.reshape(B_ * N, Cc), compute_dtype)
+            wqkv, bqkv = self.qkv.packed(compute_dtype)
+            qkv = ops.linear(a, wqkv, bqkv)
+            # every window is a 4x4 "image" of its own: window-row order = raster order
+            o = ops.window4_attention(qkv, packing.pack_rpb_table4(self.relative_position_bias_table, self.relative_position_index), B_, 4, 4,
+                                      self.num_heads)
+            y = ops.linear(o, _to_compute(self.proj.weight, compute_dtype), self.proj.bias.detach().float(), 0)
+            return y.reshape(B_, N, Cc).to(x.dtype)
         if N != 64:
             raise UformerHipError("window attention needs 8x8 = 64 tokens per window")
         if H is None or W is None:  # any geometry with the right window count serves a dense mask
@@ -261,8 +274,13 @@ class LeWinTransformerBlock(nn.Module):
             self.shift_size = 0
             self.win_size = min(self.input_resolution)
         assert 0 <= self.shift_size < self.win_size, "shift_size must in 0-win_size"
-        if self.win_size != 8 or win_size != 8:
-            raise NotImplementedError("the HIP path is built for win_size 8 (constructor resolution must be >= 8)")
+        # built: window 8, and window 4 clamped from 8 (the bottleneck of a model built for 64x64 patches)
+        if win_size != 8 or self.win_size not in (4, 8):
+            raise NotImplementedError(f"the HIP path is built for win_size 8 and for a window clamped to 4; this block would need window "
+                                      f"{self.win_size} (input_resolution {tuple(self.input_resolution)}, win_size {win_size})")
+        if self.win_size == 4 and modulator:
+            raise NotImplementedError("a 4x4-window block with a modulator: the reference's (64, C) embedding (model.py:868-869) does not broadcast "
+                                      "onto 16-token windows (model.py:967-969)")
         self.modulator = nn.Embedding(win_size * win_size, dim) if modulator else None
         self.cross_modulator = None
         self.norm1 = norm_layer(dim)
@@ -281,7 +299,10 @@ class LeWinTransformerBlock(nn.Module):
         sd = {k: v for k, v in self.state_dict(keep_vars=True).items()}
         key = (dtype, tuple((v.data_ptr(), v._version) for v in sd.values()))
         if self._packed is None or self._packed[0] != key:
-            bp, keep = packing.pack_block(sd, "", self.num_heads, self.shift_size, dtype)
+            if self.win_size == 4:
+                bp, keep = packing.pack_block4(sd, "", self.num_heads, dtype)
+            else:
+                bp, keep = packing.pack_block(sd, "", self.num_heads, self.shift_size, dtype)
             self._packed = (key, bp, keep)
         return self._packed[1]
 
@@ -319,6 +340,17 @@ class LeWinTransformerBlock(nn.Module):
             raise UformerHipError("LeWinTransformerBlock runs on the GPU only; there is no CPU path")
         dt = ops.uf_dtype(compute_dtype)
         y = x.detach().float().contiguous().clone()
+        if self.win_size == 4:
+            if mask is not None:
+                raise NotImplementedError("the mask argument is not supported by 4x4-window blocks (no reference script passes it)")
+            with torch.cuda.device(x.device):
+                lib = _lib.load()
+                nbytes = lib.uf_block_workspace_bytes(B * L, Cc, dt)
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+                bp = self._pack(compute_dtype)
+                _lib.check(lib.uf_lewin_block4_fwd(bp, y.data_ptr(), Cc, B, H, W, Cc, None, None, dt, ws.data_ptr(), nbytes,
+                                                   torch.cuda.current_stream().cuda_stream), "uf_lewin_block4_fwd")
+            return y.to(x.dtype)
         um = self.user_attn_mask(mask, H, W) if mask is not None else None
         with torch.cuda.device(x.device):
             lib = _lib.load()
@@ -386,6 +418,12 @@ class Uformer(nn.Module):
         self.cfg = UformerConfig(img_size=img_size, in_chans=in_chans, dd_in=dd_in, embed_dim=embed_dim,
                                  depths=tuple(depths), num_heads=tuple(num_heads), win_size=win_size, mlp_ratio=mlp_ratio,
                                  modulator=modulator, shift_flag=shift_flag)
+        bad = self.cfg.unsupported_clamp() if win_size == 8 else None
+        if bad is not None:       # model.py:863-866 clamps a stage's window to its resolution; built: 8, and 4 for the bottleneck alone
+            s_, res_, win_ = bad
+            raise NotImplementedError(f"img_size={img_size}: stage {STAGES[s_]} has resolution {res_}, so the reference would run it on "
+                                      f"{win_}x{win_} windows; the HIP path is built for 8x8 windows and, for the bottleneck (conv) alone, 4x4 "
+                                      f"(img_size // 16 == 4, e.g. 64)")
         enc_dpr = [x.item() for x in torch.linspace(0, drop_path_rate, sum(depths[:self.num_enc_layers]))]
         conv_dpr = [drop_path_rate] * depths[4]
         dec_dpr = enc_dpr[::-1]
@@ -514,6 +552,14 @@ class Uformer(nn.Module):
 
     # ---- forward -----------------------------------------------------------------------------
     def forward(self, x: Tensor, mask: Optional[Tensor] = None) -> Tensor:
+        if self.cfg.stage_windows()[4] == 4 and x.dim() == 4:     # built for 64x64 patches: 4 downsamplings x the bottleneck's window 4
+            for name, n in (("H", x.shape[2]), ("W", x.shape[3])):
+                if n % 64 or n <= 0:
+                    raise UformerHipError(f"{name}={n} must be a positive multiple of 64 (a model built for img_size {self.reso}: "
+                                          f"4 downsamplings x the bottleneck's 4x4 windows)")
+            if mask is not None:
+                raise NotImplementedError("the mask argument is not supported by a model whose bottleneck runs on 4x4 windows (img_size 64; "
+                                          "no reference script passes it)")
         if not x.is_cuda:
             raise UformerHipError("uformer_amd.Uformer runs on an MI355X only; there is no CPU fallback "
                                   "(the CPU oracle lives in oracle/ and is test infrastructure)")
@@ -544,6 +590,15 @@ class Uformer(nn.Module):
         with torch.cuda.device(x.device):
             lib = _lib.load()
             pk = self._get_packed(x.device)
+            if pk.win4:      # built for 64x64 patches: the bottleneck runs on 4x4 windows (uf_uformer_win4_fwd)
+                need = lib.uf_uformer_win4_workspace_bytes(pk.desc, B, H, W, dt)
+                if need == 0:
+                    raise UformerHipError("uf_uformer_win4_workspace_bytes: " + _lib.last_error())
+                ws = self._workspace(need, x.device)
+                out = torch.empty((B, self.in_chans, H, W), dtype=torch.float32, device=x.device)
+                _lib.check(lib.uf_uformer_win4_fwd(pk.desc, pk.bneck, xin.data_ptr(), out.data_ptr(), B, H, W, dt, ws.data_ptr(),
+                                                   ws.numel(), torch.cuda.current_stream().cuda_stream), "uf_uformer_win4_fwd")
+                return out.to(x.dtype)
             need = lib.uf_uformer_workspace_bytes(pk.desc, B, H, W, dt)
             if need == 0:
                 raise UformerHipError("uf_uformer_workspace_bytes: " + _lib.last_error())
@@ -606,9 +661,10 @@ class Uformer(nn.Module):
         total += self.input_proj.flops(r, r) + self.output_proj.flops(r, r)
         dims = self.cfg.stage_dims()
         div = self.cfg.stage_res_div()
+        wins = self.cfg.stage_windows()
         for s in range(9):
             L = (r // div[s]) ** 2
-            total += self.cfg.depths[s] * L * dims[s] * (12 * dims[s] + 2 * 64 + 36)
+            total += self.cfg.depths[s] * L * dims[s] * (12 * dims[s] + 2 * wins[s] ** 2 + 36)
         for s in range(4):
             L = (r // div[s]) ** 2
             total += (L // 4) * dims[s] * 2 * dims[s] * 16

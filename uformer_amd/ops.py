@@ -75,9 +75,12 @@ def _c(t: Tensor, dtype: Optional[torch.dtype] = None) -> Tensor:
 # a1-a4 index ops
 # ---------------------------------------------------------------------------------------
 def window_partition(x: Tensor, win_size: int = 8, shift: int = 0) -> Tensor:
-    """(B,H,W,C) -> (B*nW, 8, 8, C).  model.py:704-715; ``shift`` folds torch.roll (:957)."""
+    """(B,H,W,C) -> (B*nW, 8, 8, C).  model.py:704-715; ``shift`` folds torch.roll (:957).  ``win_size`` 4 (no shift): the
+    4x4 windows of a bottleneck built for 64x64 patches."""
+    if win_size == 4 and shift == 0:
+        return _window4_copy(x, reverse=False)
     if win_size != 8:
-        raise UformerHipError("win_size must be 8")
+        raise UformerHipError("win_size must be 8 (or 4 without a shift)")
     _dev(x)
     B, H, W, Cc = x.shape
     x = _c(x)
@@ -91,9 +94,11 @@ def window_partition(x: Tensor, win_size: int = 8, shift: int = 0) -> Tensor:
 
 
 def window_reverse(windows: Tensor, win_size: int, H: int, W: int, shift: int = 0) -> Tensor:
-    """(B*nW, 8, 8, C) -> (B,H,W,C).  model.py:717-726; ``shift`` folds the roll back (:980)."""
+    """(B*nW, 8, 8, C) -> (B,H,W,C).  model.py:717-726; ``shift`` folds the roll back (:980).  ``win_size`` 4: see window_partition."""
+    if win_size == 4 and shift == 0:
+        return _window4_copy(windows, reverse=True, H=H, W=W)
     if win_size != 8:
-        raise UformerHipError("win_size must be 8")
+        raise UformerHipError("win_size must be 8 (or 4 without a shift)")
     _dev(windows)
     windows = _c(windows)
     Cc = windows.shape[-1]
@@ -103,6 +108,73 @@ def window_reverse(windows: Tensor, win_size: int, H: int, W: int, shift: int = 
     with torch.cuda.device(windows.device):
         _lib.check(_lib.load().uf_window_reverse(_ptr(windows), _ptr(out), B, H, W, Cc, shift, windows.element_size(),
                                                  _stream()), "uf_window_reverse")
+    return out
+
+
+def _window4_copy(x: Tensor, reverse: bool, H: int = 0, W: int = 0) -> Tensor:
+    """uf_window4_partition ((B,H,W,C) -> (B*nW,4,4,C)) or uf_window4_reverse ((B*nW,4,4,C) -> (B,H,W,C))."""
+    _dev(x)
+    x = _c(x)
+    if x.element_size() not in (2, 4):
+        raise UformerHipError("window ops support 2- and 4-byte elements")
+    Cc = x.shape[-1]
+    if reverse:
+        nW = (H // 4) * (W // 4)
+        if nW == 0 or H % 4 or W % 4 or x.shape[0] % nW:
+            raise UformerHipError(f"window_reverse at 4: H={H} W={W} do not tile {tuple(x.shape)}")
+        B = x.shape[0] // nW
+        out = torch.empty((B, H, W, Cc), dtype=x.dtype, device=x.device)
+        fn = "uf_window4_reverse"
+    else:
+        B, H, W, _ = x.shape
+        out = torch.empty((B * (H // 4) * (W // 4), 4, 4, Cc), dtype=x.dtype, device=x.device)
+        fn = "uf_window4_partition"
+    with torch.cuda.device(x.device):
+        _lib.check(getattr(_lib.load(), fn)(_ptr(x), _ptr(out), B, H, W, Cc, x.element_size(), _stream()), fn)
+    return out
+
+
+def window4_attention(qkv: Tensor, rpb4: Tensor, B: int, H: int, W: int, heads: int) -> Tensor:
+    """4x4-window attention on raster rows: qkv T (B*H*W, 3C) = the q|k|v projection outputs (unscaled), rpb4 f32 (heads, 49)
+    (packing.pack_rpb_table4) -> o T (B*H*W, C), heads merged.  model.py:494-519 at win 4, no mask."""
+    _dev(qkv, rpb4)
+    qkv = _c(qkv)
+    M, C3 = qkv.shape
+    C = C3 // 3
+    if M != B * H * W or C3 != 3 * C:
+        raise UformerHipError(f"window4_attention: qkv {tuple(qkv.shape)} does not match B*H*W = {B * H * W}")
+    out = torch.empty(M, C, dtype=qkv.dtype, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        _lib.check(_lib.load().uf_window4_attention_fwd(_ptr(qkv), C3, _ptr(_c(rpb4, torch.float32)), _ptr(out), C, B, H, W, C, heads,
+                                                        uf_dtype(qkv.dtype), _stream()), "uf_window4_attention_fwd")
+    return out
+
+
+def window4_attention_bwd(qkv: Tensor, rpb4: Tensor, do: Tensor, B: int, H: int, W: int, heads: int) -> Tuple[Tensor, Tensor]:
+    """Backward of window4_attention: (dqkv T (B*H*W, 3C), dscore f32 (n_windows, heads, 16, 16))."""
+    _dev(qkv, rpb4, do)
+    qkv = _c(qkv)
+    do = _c(do, qkv.dtype)
+    M, C3 = qkv.shape
+    C = C3 // 3
+    if M != B * H * W or do.shape != (M, C):
+        raise UformerHipError(f"window4_attention_bwd: qkv {tuple(qkv.shape)} / do {tuple(do.shape)} do not match B*H*W = {B * H * W}")
+    dqkv = torch.empty_like(qkv)
+    dscore = torch.empty(B * (H // 4) * (W // 4), heads, 16, 16, dtype=torch.float32, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        _lib.check(_lib.load().uf_window4_attention_bwd(_ptr(qkv), C3, _ptr(_c(rpb4, torch.float32)), _ptr(do), C, _ptr(dqkv), C3, _ptr(dscore),
+                                                        B, H, W, C, heads, uf_dtype(qkv.dtype), _stream()), "uf_window4_attention_bwd")
+    return dqkv, dscore
+
+
+def rpb4_table_grad(dscore: Tensor) -> Tensor:
+    """(n_windows, heads, 16, 16) score gradient -> (49, heads) relative_position_bias_table gradient of a 4x4-window block."""
+    _dev(dscore)
+    dscore = _c(dscore, torch.float32)
+    nW, heads = dscore.shape[0], dscore.shape[1]
+    out = torch.empty(49, heads, dtype=torch.float32, device=dscore.device)
+    with torch.cuda.device(dscore.device):
+        _lib.check(_lib.load().uf_rpb4_table_grad(_ptr(dscore), _ptr(out), nW, heads, _stream()), "uf_rpb4_table_grad")
     return out
 
 

@@ -49,6 +49,25 @@ def pack_rpb_table(dense: Tensor):
     return tab.contiguous()
 
 
+def pack_rpb_table4(table: Tensor, index: Tensor) -> Tensor:
+    """4x4-window bias: (49, heads) table + (16, 16) index -> (heads, 49) f32 T4[h][(dy+3)*7 + dx+3], dy = yq-yk, dx = xq-xk,
+    the layout the 4x4-window kernels read (bias(q, k) = T4[h][Toeplitz entry of (q, k)], model.py:467-477 at win 4).  Raises
+    unless the bias IS Toeplitz in (dy, dx) -- always true for the reference's relative_position_index."""
+    dense = rpb_dense(table, index)                                  # (heads, 16, 16)
+    if dense.shape[1:] != (16, 16):
+        raise ValueError(f"pack_rpb_table4: expected a (16, 16) relative_position_index, got {tuple(index.shape)}")
+    c = torch.arange(4, device=dense.device)
+    ys, xs = torch.meshgrid(c, c, indexing="ij")
+    ys, xs = ys.reshape(-1), xs.reshape(-1)
+    ent = (ys[:, None] - ys[None, :] + 3) * 7 + (xs[:, None] - xs[None, :] + 3)     # (16, 16) entry of each (q, k) pair
+    tab = torch.zeros(dense.shape[0], 49, dtype=torch.float32, device=dense.device)
+    tab[:, ent] = dense
+    if not torch.equal(tab[:, ent], dense):
+        raise ValueError("pack_rpb_table4: the relative-position bias is not Toeplitz in (dy, dx); the 4x4-window kernels need the "
+                         "reference's relative_position_index")
+    return tab.contiguous()
+
+
 def pack_dwconv(w: Tensor) -> Tensor:
     """(C,1,3,3) -> (9,C) tap-major f32."""
     return w.detach().reshape(w.shape[0], 9).t().contiguous().float()
@@ -108,6 +127,31 @@ def pack_block(sd: Dict[str, Tensor], prefix: str, heads: int, shift: int, dtype
     return bp, keep
 
 
+def pack_block4(sd: Dict[str, Tensor], prefix: str, heads: int, dtype: torch.dtype):
+    """``uf_block4_params`` of a 4x4-window block (row-major T weights, the (heads, 49) bias table): returns (Block4Params, keepalive)."""
+    if (prefix + "modulator.weight") in sd:
+        raise NotImplementedError("a 4x4-window block with a modulator: the reference adds a (64, C) embedding to 16-token windows, "
+                                  "which does not broadcast (model.py:868-869, :967-969)")
+    f = lambda k: sd[prefix + k].detach().float().clone().contiguous()  # noqa: E731
+    t = lambda k: sd[prefix + k].detach().to(dtype, copy=True).contiguous()  # noqa: E731
+    keep: Dict[str, Tensor] = {
+        "norm1_w": f("norm1.weight"), "norm1_b": f("norm1.bias"), "norm2_w": f("norm2.weight"), "norm2_b": f("norm2.bias"),
+        "rpb4": pack_rpb_table4(sd[prefix + "attn.relative_position_bias_table"], sd[prefix + "attn.relative_position_index"]),
+        "wqkv": torch.cat([sd[prefix + "attn.qkv.to_q.weight"].detach(), sd[prefix + "attn.qkv.to_kv.weight"].detach()], 0).to(dtype).contiguous(),
+        "bqkv": torch.cat([sd[prefix + "attn.qkv.to_q.bias"].detach(), sd[prefix + "attn.qkv.to_kv.bias"].detach()], 0).float().contiguous(),
+        "wproj": t("attn.proj.weight"), "bproj": f("attn.proj.bias"),
+        "w1": t("mlp.linear1.0.weight"), "b1": f("mlp.linear1.0.bias"),
+        "wdw9": pack_dwconv(sd[prefix + "mlp.dwconv.0.weight"]), "bdw": f("mlp.dwconv.0.bias"),
+        "w2": t("mlp.linear2.0.weight"), "b2": f("mlp.linear2.0.bias"),
+    }
+    bp = _lib.Block4Params()
+    for name, _ in _lib.Block4Params._fields_:
+        if name != "heads":
+            setattr(bp, name, keep[name].data_ptr())
+    bp.heads = int(heads)
+    return bp, keep
+
+
 class PackedModel:
     """All packed weights of one ``Uformer`` + the ``uf_model_desc`` that points at them."""
 
@@ -116,13 +160,22 @@ class PackedModel:
         self.dtype = dtype
         self.keep: List[object] = []
         shifts = cfg.block_shifts()
+        wins = cfg.stage_windows()
         n_blocks = sum(cfg.depths)
         self.blocks = (_lib.BlockParams * n_blocks)()
+        # 4x4-window bottleneck (img_size 64): its blocks go to uf_uformer_win4_fwd as uf_block4_params; their uf_block_params
+        # slots stay zeroed (the whole-model entry skips them)
+        self.win4 = wins[4] == 4
+        self.bneck = (_lib.Block4Params * max(1, cfg.depths[4]))() if self.win4 else None
         i = 0
         for s in range(9):
             for b in range(cfg.depths[s]):
-                bp, keep = pack_block(sd, f"{STAGES[s]}.blocks.{b}.", cfg.num_heads[s], shifts[s][b], dtype)
-                self.blocks[i] = bp
+                if wins[s] == 4:
+                    bp4, keep = pack_block4(sd, f"{STAGES[s]}.blocks.{b}.", cfg.num_heads[s], dtype)
+                    self.bneck[b] = bp4
+                else:
+                    bp, keep = pack_block(sd, f"{STAGES[s]}.blocks.{b}.", cfg.num_heads[s], shifts[s][b], dtype)
+                    self.blocks[i] = bp
                 self.keep.append(keep)
                 i += 1
         d = _lib.ModelDesc()

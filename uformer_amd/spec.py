@@ -47,6 +47,15 @@ class UformerConfig:
         """Only decoder stages receive ``modulator`` (model.py:1197,1213,1229,1245)."""
         return self.modulator and s >= 5
 
+    def stage_windows(self) -> List[int]:
+        """Constructor-time window of each stage: ``win_size``, clamped to the stage's resolution where that is not larger
+        (model.py:863-866).  At img_size 64 the bottleneck (resolution 4) gets 4x4 windows."""
+        out = []
+        for s in range(9):
+            res = self.img_size // self.stage_res_div()[s]
+            out.append(res if res <= self.win_size else self.win_size)
+        return out
+
     def block_shifts(self) -> List[List[int]]:
         """Constructor-time shift of every block (model.py:1030 then the clamp :863-866)."""
         out = []
@@ -60,6 +69,19 @@ class UformerConfig:
                 row.append(sh)
             out.append(row)
         return out
+
+    def unsupported_clamp(self):
+        """None if every stage runs on a window this project builds (8, or 4 for the bottleneck alone), else (stage index,
+        resolution, window the reference would use) of the first stage that does not."""
+        for s, win in enumerate(self.stage_windows()):
+            if win == self.win_size == 8 or (s == 4 and win == 4):
+                continue
+            return s, self.img_size // self.stage_res_div()[s], win
+        return None
+
+    def input_multiple(self) -> int:
+        """H and W of a forward input must be multiples of this: 2^s x window at every stage (128, or 64 with a 4x4 bottleneck)."""
+        return max((1 << min(s, 8 - s)) * w for s, w in enumerate(self.stage_windows()))
 
     def upsample_io(self) -> List[Tuple[int, int]]:
         """(Cin, Cout) of upsample_0..3 (model.py:1182,1198,1214,1230)."""
@@ -85,11 +107,13 @@ def arch_config(name: str, img_size: int = 256, dd_in: int = 3) -> UformerConfig
 
 # ---- state_dict layout ------------------------------------------------------------------
 def block_spec(prefix: str, C: int, heads: int, win: int, modulator: bool,
-               mlp_ratio: float = 4.0) -> Iterator[Tuple[str, Tuple[int, ...], str]]:
-    """(key, shape, kind) of one LeWinTransformerBlock, in registration order."""
+               mlp_ratio: float = 4.0, mod_win: int = None) -> Iterator[Tuple[str, Tuple[int, ...], str]]:
+    """(key, shape, kind) of one LeWinTransformerBlock, in registration order.  ``win``: the block's (clamped) window;
+    ``mod_win`` (default ``win``): the unclamped window the modulator embedding is sized by (model.py:868-869)."""
     hid = int(C * mlp_ratio)
     if modulator:
-        yield prefix + "modulator.weight", (win * win, C), "embedding"
+        mw = win if mod_win is None else mod_win
+        yield prefix + "modulator.weight", (mw * mw, C), "embedding"
     yield prefix + "norm1.weight", (C,), "ln_w"
     yield prefix + "norm1.bias", (C,), "ln_b"
     yield prefix + "attn.relative_position_bias_table", ((2 * win - 1) ** 2, heads), "rpb"
@@ -114,6 +138,7 @@ def state_dict_spec(cfg: UformerConfig) -> List[Tuple[str, Tuple[int, ...], str]
     """Every key of the reference ``Uformer.state_dict()`` with shape, in reference order."""
     e = cfg.embed_dim
     dims = cfg.stage_dims()
+    wins = cfg.stage_windows()
     spec: List[Tuple[str, Tuple[int, ...], str]] = []
     spec.append(("input_proj.proj.0.weight", (e, cfg.dd_in, 3, 3), "conv_w"))
     spec.append(("input_proj.proj.0.bias", (e,), "conv_b"))
@@ -123,7 +148,7 @@ def state_dict_spec(cfg: UformerConfig) -> List[Tuple[str, Tuple[int, ...], str]
     def stage(s: int):
         for i in range(cfg.depths[s]):
             spec.extend(block_spec(f"{STAGES[s]}.blocks.{i}.", dims[s], cfg.num_heads[s],
-                                   cfg.win_size, cfg.stage_has_modulator(s), cfg.mlp_ratio))
+                                   wins[s], cfg.stage_has_modulator(s), cfg.mlp_ratio, mod_win=cfg.win_size))
 
     for s in range(4):
         stage(s)
@@ -158,7 +183,7 @@ def synth_state_dict(cfg: UformerConfig, seed: int = 1234) -> Dict[str, torch.Te
         h = int.from_bytes(hashlib.sha256(f"{seed}:{key}".encode()).digest()[:6], "little")
         g = torch.Generator().manual_seed(h)
         if kind == "rpi":
-            out[key] = relative_position_index(cfg.win_size)
+            out[key] = relative_position_index(math.isqrt(shape[0]))
             continue
         n = torch.randn(shape, generator=g, dtype=torch.float32)
         if kind == "linear_w":

@@ -54,6 +54,11 @@ class BlockPack:
     def __init__(self, p: Dict[str, Tensor], prefix: str, heads: int, shift: int, T: torch.dtype, fused: bool):
         f = lambda k: p[prefix + k]                                             # noqa: E731
         self.prefix, self.heads, self.shift, self.T = prefix, heads, shift, T
+        self.win = block_window(p, prefix)
+        self.rpb4 = None
+        if self.win == 4:      # 4x4-window block: the (heads, 49) table the window-4 kernels read; no fused form
+            self.rpb4 = packing.pack_rpb_table4(f("attn.relative_position_bias_table"), f("attn.relative_position_index"))
+            fused = False
         self.mod = f("modulator.weight") if (prefix + "modulator.weight") in p else None
         self.wqkv = torch.cat([f("attn.qkv.to_q.weight"), f("attn.qkv.to_kv.weight")], 0).to(T)
         self.bqkv = torch.cat([f("attn.qkv.to_q.bias"), f("attn.qkv.to_kv.bias")], 0)
@@ -158,9 +163,49 @@ class NativeBlockPack:
         self.mod = p[prefix + "modulator.weight"] if (prefix + "modulator.weight") in p else None
 
 
+_STD_INDEX4: Dict[Tuple[int, int], bool] = {}
+_PACK4_DUMMY: Dict[Tuple[int, str], Tuple[Tensor, Tensor]] = {}
+_PACK4_KEYS = ("norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias", "attn.qkv.to_q.weight", "attn.qkv.to_q.bias", "attn.qkv.to_kv.weight",
+               "attn.qkv.to_kv.bias", "attn.proj.weight", "attn.proj.bias", "mlp.linear1.0.weight", "mlp.linear1.0.bias", "mlp.dwconv.0.weight",
+               "mlp.dwconv.0.bias", "mlp.linear2.0.weight", "mlp.linear2.0.bias")
+
+
+def native_block4_pack(p: Dict[str, Tensor], prefix: str, heads: int, T: torch.dtype) -> NativeBlockPack:
+    """The per-step operand pack of a 4x4-window block without ATen compute: uf_pack_block_train makes every operand but the bias table
+    (it is built for the (225, heads) table and the (64, 64) index, so it is handed a zero table and the standard index, and the bias it
+    derives from them is never read), and the (heads, 49) table of the window-4 kernels is the reference's (49, heads) table transposed
+    (packing.pack_rpb_table4 of the reference's index, which is checked once per index buffer)."""
+    table, idx = p[prefix + "attn.relative_position_bias_table"].detach(), p[prefix + "attn.relative_position_index"]
+    dev = table.device
+    dkey = (heads, str(dev))
+    if dkey not in _PACK4_DUMMY:
+        from .spec import relative_position_index
+        _PACK4_DUMMY[dkey] = (torch.zeros(225, heads, device=dev), relative_position_index(8).to(dev))
+    sub = {prefix + k: p[prefix + k] for k in _PACK4_KEYS}
+    sub[prefix + "attn.relative_position_bias_table"], sub[prefix + "attn.relative_position_index"] = _PACK4_DUMMY[dkey]
+    pk = NativeBlockPack(sub, prefix, heads, 0, T)
+    ikey = (idx.data_ptr(), idx._version)
+    if ikey not in _STD_INDEX4:
+        from .spec import relative_position_index
+        _STD_INDEX4[ikey] = bool(tuple(idx.shape) == (16, 16) and torch.equal(idx.detach().cpu().long(), relative_position_index(4)))
+    pk.rpb4 = table.float().t().contiguous() if _STD_INDEX4[ikey] else packing.pack_rpb_table4(table, idx)
+    pk.win = 4
+    return pk
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # LeWin block (model.py:908-989)
 # ------------------------------------------------------------------------------------------------------------------
+def block_window(p: Dict[str, Tensor], prefix: str = "") -> int:
+    """The block's window, from its relative-position table: (2 win - 1)^2 rows (225: 8, 49: 4 -- the bottleneck of a model
+    built for 64x64 patches, model.py:863-866)."""
+    n = p[prefix + "attn.relative_position_bias_table"].shape[0]
+    win = (math.isqrt(n) + 1) // 2
+    if (2 * win - 1) ** 2 != n or win not in (4, 8):
+        raise ops.UformerHipError(f"{prefix}attn.relative_position_bias_table has {n} rows: windows 8 (225) and 4 (49) are built")
+    return win
+
+
 def block_hw(L: int, hw: Optional[Tuple[int, int]], who: str = "LeWin block") -> Tuple[int, int]:
     """(H, W) of a (B, L, C) token map: ``hw`` when given (checked against L), else the square side the reference takes
     (model.py:910-911).  A non-square L without ``hw`` is an error, not a guess."""
@@ -181,18 +226,32 @@ def lewin_block_forward(x: Tensor, p: Dict[str, Tensor], prefix: str, heads: int
     """x: (B, L, C) f32 on the GPU -> (y, saved).  Op-by-op forward that keeps what the backward reads (also the RECOMPUTATION a
     block runs at the start of its backward).  ``drop``: None (eval) or (2, B) per-sample DropPath scales bernoulli(keep)/keep of
     the two residual branches (model.py:986-987).  ``need_y=False``: the recomputation stops before linear2 (nothing reads y).
-    ``hw``: the (H, W) of the map (needed when H != W; default: the square side of L)."""
+    ``hw``: the (H, W) of the map (needed when H != W; default: the square side of L).  The block's window (8, or 4) comes from its
+    relative-position table (block_window); a 4x4-window block runs its attention half on raster rows (window4_attention)."""
     B, L, C = x.shape
     H, W = block_hw(L, hw)
     M = B * L
     T = dtype
-    pk = pk or BlockPack(p, prefix, heads, shift, T, fused=fused_attn_covers(T, C, heads))
+    win = block_window(p, prefix)
+    pk = pk or BlockPack(p, prefix, heads, shift, T, fused=win == 8 and fused_attn_covers(T, C, heads))
     f = lambda k: p[prefix + k]                                             # noqa: E731
     x2 = x.reshape(M, C).float().contiguous()
     s1 = drop[0].float().contiguous() if drop is not None else None         # per-sample DropPath scales (B,)
     s2 = drop[1].float().contiguous() if drop is not None else None
-    fused_attn = fused_attn_covers(T, C, heads) and getattr(pk, "fused", None) is not None
-    if fused_attn:
+    fused_attn = win == 8 and fused_attn_covers(T, C, heads) and getattr(pk, "fused", None) is not None
+    q = k = vt = qkv = None
+    if win == 4:
+        # LN1 -> q|k|v -> 4x4-window attention -> proj + residual, all on raster rows (the window geometry is in the attention kernel's
+        # addressing; shift 0 and no modulator at win 4).  The block keeps these intermediates in both training forms (about 1 % of a
+        # step's activations): the recompute form's fused kernels are built for 8x8 windows.
+        if pk.mod is not None:
+            raise NotImplementedError("a 4x4-window block with a modulator: the reference's (64, C) embedding does not broadcast onto 16-token windows")
+        xn = ops.layernorm(x2, f("norm1.weight"), f("norm1.bias"), B=B, H=H, W=W, dtype=T)
+        qkv = ops.linear(xn, pk.wqkv, pk.bqkv)
+        o = ops.window4_attention(qkv, pk.rpb4, B, H, W, heads)
+        x1 = ops.linear_residual(o, pk.wp, f("attn.proj.bias"), x2, s1, B, H, W)
+        z = ops.layernorm(x1, f("norm2.weight"), f("norm2.bias"), B=B, H=H, W=W, dtype=T)
+    elif fused_attn:
         # round 6: LN1 -> q/k/v -> attention -> proj + residual -> LN2 -> linear1 in ONE launch (the fused window kernel of the inference path) with side
         # stores of every operand the backward reads, instead of the six launches below and their round trips through HBM
         x1, xn, q, k, vt, o, z, a1 = ops.lewin_attn_train_fwd(pk.fused, x2, B, H, W, heads, T, s1)
@@ -217,7 +276,7 @@ def lewin_block_forward(x: Tensor, p: Dict[str, Tensor], prefix: str, heads: int
     if need_y:
         y = ops.linear_residual(g2, pk.w2, f("mlp.linear2.0.bias"), x1, s2, B, H, W).reshape(B, L, C)     # x1 + DropPath(linear2(.))   model.py:987
     saved = dict(s1=s1, s2=s2, p=p, prefix=prefix, heads=heads, shift=shift, T=T, shape=(B, L, C), hw=(H, W), x2=x2, xn=xn, q=q, k=k, vt=vt, o=o, x1=x1, z=z, a1=a1,
-                 h1=h1, c=c, g2=g2, pk=pk, mod=pk.mod is not None)
+                 h1=h1, c=c, g2=g2, pk=pk, mod=pk.mod is not None, win=win, qkv=qkv)
     return y, saved
 
 
@@ -304,6 +363,32 @@ def lewin_block_backward(sv: Saved, dy: Tensor, dyT: Optional[Tensor] = None, ne
         da1 = ops.dwconv3x3_mul_dgelu(dc, pk.w9_flip, sv["a1"].reshape(B, H, W, 4 * C)).reshape(M, 4 * C)   # flipped-tap stencil, times GELU'(a1)
     g[prefix + "mlp.linear1.0.weight"], g[prefix + "mlp.linear1.0.bias"] = side.run(lambda: ops.linear_wgrad(da1, sv["z"]))
     dz = _input_grad(da1, pk.w1_t)
+    if sv.get("win", 8) == 4:
+        # 4x4-window block: the attention half on raster rows (no partition, roll or modulator)                    (model.py:951-986)
+        if _FUSE_FORK and dz.dtype == T:
+            dx1, g[prefix + "norm2.weight"], g[prefix + "norm2.bias"], dyw = ops.layernorm_bwd_fused(sv["x1"], f("norm2.weight"), dz, B, H, W, add=dyf,
+                                                                                                     cast=dict(scale=sv["s1"], windowed=False, shift=0))
+        else:
+            dx1, g[prefix + "norm2.weight"], g[prefix + "norm2.bias"] = ops.layernorm_bwd_fused(sv["x1"], f("norm2.weight"), dz, B, H, W)
+            dx1, dyw = ops.grad_fork(dx1, dyf, sv["s1"], B, H, W, T, want_sum=True)
+        g[prefix + "attn.proj.weight"], g[prefix + "attn.proj.bias"] = side.run(lambda: ops.linear_wgrad(dyw, sv["o"]))
+        do = _input_grad(dyw, pk.wp_t)
+        dqkv, dscore = ops.window4_attention_bwd(sv["qkv"], pk.rpb4, do, B, H, W, heads)
+        g[prefix + "attn.relative_position_bias_table"] = side.run(lambda: ops.rpb4_table_grad(dscore))   # fixed-order gather: deterministic
+        dWqkv, dbqkv = side.run(lambda: ops.linear_wgrad(dqkv, sv["xn"]))
+        g[prefix + "attn.qkv.to_q.weight"], g[prefix + "attn.qkv.to_kv.weight"] = dWqkv[:C], dWqkv[C:]
+        g[prefix + "attn.qkv.to_q.bias"], g[prefix + "attn.qkv.to_kv.bias"] = dbqkv[:C], dbqkv[C:]
+        dxn = _input_grad(dqkv, pk.wqkv_t)
+        if next_scale is not _NO_CAST and _FUSE_FORK and dxn.dtype == T:
+            dx, g[prefix + "norm1.weight"], g[prefix + "norm1.bias"], dyT_next = ops.layernorm_bwd_fused(sv["x2"], f("norm1.weight"), dxn, B, H, W, add=dx1,
+                                                                                                         cast=dict(scale=next_scale, windowed=False))
+            side.join()
+            return dx.reshape(B, L, C), g, dyT_next
+        dx, g[prefix + "norm1.weight"], g[prefix + "norm1.bias"] = ops.layernorm_bwd_fused(sv["x2"], f("norm1.weight"), dxn, B, H, W, add=dx1)
+        side.join()
+        if next_scale is not _NO_CAST:
+            return dx.reshape(B, L, C), g, None
+        return dx.reshape(B, L, C), g
     # attention half: proj -> attention -> qkv -> (+modulator) -> partition/roll -> LN1              (model.py:951-986)
     # dx1 = LN2-path gradient + dy (the residual), and the (scaled) gradient entering the attention branch in window order
     if _FUSE_FORK and dz.dtype == T:                                        # both from the LayerNorm backward kernel
@@ -468,7 +553,12 @@ class UformerTape:
             warnings.warn("the recompute form was selected (use_checkpoint=True, recompute=True, or chosen from the free memory), but no stage has head_dim 32 (the fused kernels the recompute form is built on): every block keeps its "
                           "intermediates (memory ~18x the recompute form)", stacklevel=2)
         shifts = cfg.block_shifts()
+        wins = self.wins = cfg.stage_windows()
         div = cfg.stage_res_div()
+        mult = cfg.input_multiple()
+        for name, n in (("H", H), ("W", W)):
+            if wins[4] == 4 and (n % mult or n <= 0):      # (the 8-window model's kernels report their own shape errors)
+                raise ops.UformerHipError(f"{name}={n} must be a positive multiple of {mult} (4 downsamplings x the bottleneck's window {wins[4]})")
         res = self.res = [(H // div[s], W // div[s]) for s in range(9)]      # (height, width) per stage
         first = [sum(cfg.depths[:s]) for s in range(9)]
         self.saved_blocks: List[List[Saved]] = [[] for _ in range(9)]
@@ -484,11 +574,15 @@ class UformerTape:
                 dr = self.drop[2 * bi:2 * bi + 2] if self.drop is not None else None
                 # the fused kernels (and the block-level C backward built on them) cover head_dim 32; a head_dim-16 block (Uformer_T,
                 # utils/model_utils.py:66-67) takes the op-by-op forward that keeps its intermediates and the op-level backward
-                fusable = self.recompute and C == 32 * cfg.num_heads[s]
+                # (a 4x4-window block -- the bottleneck of a model built for 64x64 patches -- keeps its intermediates in both forms)
+                fusable = self.recompute and C == 32 * cfg.num_heads[s] and wins[s] == 8
                 # uf_pack_block_train (5 launches) covers C % 32 == 0; its pack also serves the op-by-op form as tensor views
-                native = C % 32 == 0 and C % cfg.num_heads[s] == 0 and _NATIVE_PACK
-                pk = self.packs[prefix] = (NativeBlockPack(sd, prefix, cfg.num_heads[s], shifts[s][i], T) if native else
-                                           BlockPack(sd, prefix, cfg.num_heads[s], shifts[s][i], T, fused=fusable or fused_attn_covers(T, C, cfg.num_heads[s])))
+                native = C % 32 == 0 and C % cfg.num_heads[s] == 0 and _NATIVE_PACK and wins[s] == 8
+                if wins[s] == 4 and C % 32 == 0 and _NATIVE_PACK:
+                    pk = self.packs[prefix] = native_block4_pack(sd, prefix, cfg.num_heads[s], T)
+                else:
+                    pk = self.packs[prefix] = (NativeBlockPack(sd, prefix, cfg.num_heads[s], shifts[s][i], T) if native else
+                                               BlockPack(sd, prefix, cfg.num_heads[s], shifts[s][i], T, fused=fusable or fused_attn_covers(T, C, cfg.num_heads[s])))
                 if fusable:                                                     # fused kernels; the block's input is all that is kept
                     y = ops.lewin_block_train_fwd(pk.fused, t, B, res[s][0], res[s][1], T, None if dr is None else dr[0], None if dr is None else dr[1])
                     self.saved_blocks[s].append(dict(x=t, drop=dr, pk=pk))
@@ -530,7 +624,8 @@ class UformerTape:
     def _block_ws(self, s: int) -> Tensor:
         """one workspace for every block backward of the sweep (sized for the largest stage)"""
         if getattr(self, "_bws", None) is None:
-            need = max(ops.lewin_block_bwd_workspace_bytes(self.B, rh, rw, self.stage_C[i], self.cfg.num_heads[i], self.T) for i, (rh, rw) in enumerate(self.res))
+            need = max(ops.lewin_block_bwd_workspace_bytes(self.B, rh, rw, self.stage_C[i], self.cfg.num_heads[i], self.T) for i, (rh, rw) in enumerate(self.res)
+                       if self.wins[i] == 8)
             self._bws = torch.empty(need, dtype=torch.uint8, device=self.img.device)
         return self._bws
 
