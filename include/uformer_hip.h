@@ -575,6 +575,53 @@ size_t uf_uformer_win4_workspace_bytes(const uf_model_desc* d, int B, int H, int
 int uf_uformer_win4_fwd(const uf_model_desc* d, const uf_block4_params* bottleneck, const float* img, float* out, int B, int H, int W,
                         uf_dtype dtype, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * UNet baseline (reference model.py:83-174: ConvBlock, UNet; get_arch('UNet')).  Dense convolutions as implicit GEMMs on MFMA:
+ * a workgroup stages its tile of input pixels plus the halo in LDS once per 32 input channels and streams the weight from L2.
+ *   x       f32 token rows [B][H][W] of Cin channels with row stride ld_x (Cin and ld_x multiples of 4, x 16-byte aligned);
+ *   w_pk    T[Cout_p][k*k*Cin_p] (uf_conv_packed_elems elements, 16-byte aligned), element [n][(ky*k + kx)*Cin_p + c] = weight[n][c][ky][kx]
+ *           of the (Cout, Cin, k, k) state_dict tensor, Cout_p = Cout rounded up to 64, Cin_p = Cin rounded up to 32, zero padded;
+ *   out     f32 rows of stride ld_o (Cout channels written), e.g. the skip half of a decoder concat buffer.
+ * ------------------------------------------------------------------------------------------------------------------------- */
+size_t uf_conv_packed_elems(int Cout, int Cin, int k);
+/* 3x3 stride 1 pad 1.  epilogue:
+ *   0  out = acc + bias
+ *   1  out = LeakyReLU(acc + bias)                       (slope 0.01, nn.LeakyReLU())
+ *   2  out = LeakyReLU(acc + bias) + aux                 (ConvBlock: block(x) + conv11(x), aux = the conv11 rows, stride ld_aux)
+ *   3  out = acc * LeakyReLU'(aux), no bias              (input gradient: w_pk packed from the flipped, transposed weight
+ *                                                         w'[c][n][2-ky][2-kx], aux = the stored LeakyReLU output, its sign picks the slope)
+ * accumulate = 1 adds the result to what out holds. */
+int uf_conv3x3_fwd(const float* x, int ld_x, const void* w_pk, const float* bias, const float* aux, int ld_aux, float* out, int ld_o,
+                   int B, int H, int W, int Cin, int Cout, int epilogue, int accumulate, uf_dtype dtype, void* stream);
+/* 1x1 (ConvBlock.conv11): out = x w^T + bias, w_pk packed with k = 1. */
+int uf_conv1x1_fwd(const float* x, int ld_x, const void* w_pk, const float* bias, float* out, int ld_o, int B, int H, int W,
+                   int Cin, int Cout, uf_dtype dtype, void* stream);
+/* 4x4 stride 2 pad 1 with any Cout (UNet.pool1..4), w_pk packed with k = 4; H, W (input) even, out at (H/2, W/2). */
+int uf_conv4s2_fwd(const float* x, int ld_x, const void* w_pk, const float* bias, float* out, int ld_o, int B, int H, int W,
+                   int Cin, int Cout, uf_dtype dtype, void* stream);
+/* 1x1 of an f32 NCHW image (B,Cin,H,W), Cin <= 4 (ConvBlock1.conv11), into f32 token rows; w f32 (Cout, Cin) as in the state_dict. */
+int uf_conv1x1_nchw_fwd(const float* img, const float* w, const float* bias, float* out, int ld_o, int B, int Cin, int H, int W,
+                        int Cout, void* stream);
+
+/* Whole UNet.forward.  Index i = ConvBlock i+1.  ConvBlock1's block.0 runs on uf_input_proj_fwd (in_w27 / in_b in its layout),
+ * its conv11 on uf_conv1x1_nchw_fwd (c11_w1 f32 (dim, 3)); every other conv weight is w_pk of the matching k (w0[0] / w11[0] unused).
+ * up_w: uf_upsample_fwd's T[4 Cout][Cin]; out_w: uf_output_proj_fwd's f32 [3][9][dim] (conv10 + the input image). */
+typedef struct uf_unet_desc {
+    int32_t dim;
+    const float* in_w27;  const float* in_b;      /* ConvBlock1.block.0 */
+    const float* c11_w1;  const float* c11_b1;    /* ConvBlock1.conv11 */
+    const void* w0[9];    const float* b0[9];     /* ConvBlock*.block.0 (k = 3) */
+    const void* w2[9];    const float* b2[9];     /* ConvBlock*.block.2 (k = 3) */
+    const void* w11[9];   const float* b11[9];    /* ConvBlock*.conv11 (k = 1) */
+    const void* pool_w[4]; const float* pool_b[4]; /* pool1..4 (k = 4) */
+    const void* up_w[4];  const float* up_b[4];   /* upv6..9 */
+    const float* out_w;   const float* out_b;     /* conv10 */
+} uf_unet_desc;
+/* img, out: f32 NCHW (B,3,H,W); H and W positive multiples of 16 (H != W allowed).  No host synchronisation. */
+size_t uf_unet_workspace_bytes(const uf_unet_desc* d, int B, int H, int W, uf_dtype dtype);
+int uf_unet_fwd(const uf_unet_desc* d, const float* img, float* out, int B, int H, int W, uf_dtype dtype, void* ws, size_t ws_bytes,
+                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -66,6 +66,18 @@ class ModelDesc(C.Structure):
     ]
 
 
+class UnetDesc(C.Structure):
+    """``uf_unet_desc`` (include/uformer_hip.h)."""
+    _fields_ = [
+        ("dim", C.c_int32),
+        ("in_w27", C.c_void_p), ("in_b", C.c_void_p), ("c11_w1", C.c_void_p), ("c11_b1", C.c_void_p),
+        ("w0", C.c_void_p * 9), ("b0", C.c_void_p * 9), ("w2", C.c_void_p * 9), ("b2", C.c_void_p * 9),
+        ("w11", C.c_void_p * 9), ("b11", C.c_void_p * 9),
+        ("pool_w", C.c_void_p * 4), ("pool_b", C.c_void_p * 4), ("up_w", C.c_void_p * 4), ("up_b", C.c_void_p * 4),
+        ("out_w", C.c_void_p), ("out_b", C.c_void_p),
+    ]
+
+
 P = c_void_p
 I = c_int
 # name -> (restype, argtypes); must list every function declared in include/uformer_hip.h
@@ -166,6 +178,13 @@ SIGNATURES = {
     "uf_lewin_block4_fwd": (I, [C.POINTER(Block4Params), P, I, I, I, I, I, P, P, I, P, c_size_t, P]),
     "uf_uformer_win4_workspace_bytes": (c_size_t, [C.POINTER(ModelDesc), I, I, I, I]),
     "uf_uformer_win4_fwd": (I, [C.POINTER(ModelDesc), C.POINTER(Block4Params), P, P, I, I, I, I, P, c_size_t, P]),
+    "uf_conv_packed_elems": (c_size_t, [I, I, I]),
+    "uf_conv3x3_fwd": (I, [P, I, P, P, P, I, P, I, I, I, I, I, I, I, I, I, P]),
+    "uf_conv1x1_fwd": (I, [P, I, P, P, P, I, I, I, I, I, I, I, P]),
+    "uf_conv4s2_fwd": (I, [P, I, P, P, P, I, I, I, I, I, I, I, P]),
+    "uf_conv1x1_nchw_fwd": (I, [P, P, P, P, I, I, I, I, I, I, P]),
+    "uf_unet_workspace_bytes": (c_size_t, [C.POINTER(UnetDesc), I, I, I, I]),
+    "uf_unet_fwd": (I, [C.POINTER(UnetDesc), P, P, I, I, I, I, P, c_size_t, P]),
 }
 
 _lock = threading.Lock()

@@ -674,7 +674,147 @@ class Uformer(nn.Module):
         return total
 
 
-def get_arch(arch: str, train_ps: int = 128, dd_in: int = 3, embed_dim: int = 32, compute_dtype=torch.bfloat16) -> Uformer:
+class ConvBlock(nn.Module):
+    """model.py:83-106.  Holds the parameters (``block.0``, ``block.2``, ``conv11``); UNet.forward runs them through the C ABI."""
+
+    def __init__(self, in_channel, out_channel, strides=1):
+        super().__init__()
+        if strides != 1:
+            raise NotImplementedError(f"ConvBlock(strides={strides}): the HIP UNet runs stride-1 blocks only (the reference's UNet uses no other)")
+        self.strides = strides
+        self.in_channel = in_channel
+        self.out_channel = out_channel
+        self.block = nn.Sequential(
+            nn.Conv2d(in_channel, out_channel, kernel_size=3, stride=strides, padding=1),
+            nn.LeakyReLU(inplace=True),
+            nn.Conv2d(out_channel, out_channel, kernel_size=3, stride=strides, padding=1),
+            nn.LeakyReLU(inplace=True),
+        )
+        self.conv11 = nn.Conv2d(in_channel, out_channel, kernel_size=1, stride=strides, padding=0)
+
+    def flops(self, H, W):
+        return H * W * self.in_channel * self.out_channel * (3 * 3 + 1) + H * W * self.out_channel * self.out_channel * 3 * 3
+
+
+class UNet(nn.Module):
+    """Drop-in for the reference's conv baseline ``UNet`` (model.py:128-174): the same constructor, submodule names and
+    ``state_dict`` layout; ``forward`` is one ``uf_unet_fwd`` call (implicit-GEMM convolutions on MFMA, include/uformer_hip.h).
+    Inputs (B, 3, H, W) with H and W positive multiples of 16 (four stride-2 convolutions); H != W is allowed."""
+
+    def __init__(self, block=ConvBlock, dim=32, compute_dtype=torch.bfloat16):
+        super().__init__()
+        if compute_dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError(f"compute_dtype must be float32, bfloat16 or float16, got {compute_dtype}")
+        if dim not in (16, 32, 64, 128):
+            raise ValueError(f"UNet(dim={dim}): dim must be 16, 32, 64 or 128 (conv10 runs on the OutputProj kernel, which takes those widths)")
+        self.dim = dim
+        self.compute_dtype = compute_dtype
+        self.ConvBlock1 = ConvBlock(3, dim, strides=1)
+        self.pool1 = nn.Conv2d(dim, dim, kernel_size=4, stride=2, padding=1)
+        self.ConvBlock2 = block(dim, dim * 2, strides=1)
+        self.pool2 = nn.Conv2d(dim * 2, dim * 2, kernel_size=4, stride=2, padding=1)
+        self.ConvBlock3 = block(dim * 2, dim * 4, strides=1)
+        self.pool3 = nn.Conv2d(dim * 4, dim * 4, kernel_size=4, stride=2, padding=1)
+        self.ConvBlock4 = block(dim * 4, dim * 8, strides=1)
+        self.pool4 = nn.Conv2d(dim * 8, dim * 8, kernel_size=4, stride=2, padding=1)
+        self.ConvBlock5 = block(dim * 8, dim * 16, strides=1)
+        self.upv6 = nn.ConvTranspose2d(dim * 16, dim * 8, 2, stride=2)
+        self.ConvBlock6 = block(dim * 16, dim * 8, strides=1)
+        self.upv7 = nn.ConvTranspose2d(dim * 8, dim * 4, 2, stride=2)
+        self.ConvBlock7 = block(dim * 8, dim * 4, strides=1)
+        self.upv8 = nn.ConvTranspose2d(dim * 4, dim * 2, 2, stride=2)
+        self.ConvBlock8 = block(dim * 4, dim * 2, strides=1)
+        self.upv9 = nn.ConvTranspose2d(dim * 2, dim, 2, stride=2)
+        self.ConvBlock9 = block(dim * 2, dim, strides=1)
+        self.conv10 = nn.Conv2d(dim, 3, kernel_size=3, stride=1, padding=1)
+        self._packed = None
+        self._ws = None
+
+    MAX_WORKSPACES = Uformer.MAX_WORKSPACES
+    _workspace = Uformer._workspace
+
+    def _apply(self, fn, *a, **k):
+        self._packed = None
+        self._ws = None
+        return super()._apply(fn, *a, **k)
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        """Accepts reference checkpoints, including ``{'state_dict': ...}`` payloads and the ``module.`` prefix
+        (utils/model_utils.py:23-33)."""
+        if "state_dict" in state_dict and not any(k.startswith("ConvBlock1") for k in state_dict):
+            state_dict = state_dict["state_dict"]
+        if all(k.startswith("module.") for k in state_dict):
+            state_dict = {k[7:]: v for k, v in state_dict.items()}
+        self._packed = None
+        return super().load_state_dict(state_dict, strict=strict, **kw)
+
+    def repack(self):
+        self._packed = None
+
+    def _get_packed(self, device):
+        plist = list(self.parameters())
+        key = (self.compute_dtype, str(device), tuple(map(torch.Tensor.data_ptr, plist)), tuple(p._version for p in plist))
+        if self._packed is None or self._packed_key != key:
+            self._packed = packing.PackedUNet(self.state_dict(keep_vars=True), self.dim, self.compute_dtype)
+            self._packed_key = key
+        return self._packed
+
+    def forward(self, x: Tensor) -> Tensor:
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise UformerHipError(f"expected (B,3,H,W) input, got {tuple(x.shape)}")
+        B, _, H, W = x.shape
+        if H <= 0 or W <= 0 or H % 16 or W % 16:
+            raise UformerHipError(f"UNet: H={H} and W={W} must be positive multiples of 16 (four stride-2 convolutions)")
+        if not x.is_cuda:
+            raise UformerHipError("uformer_amd.UNet runs on an MI355X only; there is no CPU fallback")
+        if torch.is_grad_enabled() and (self.training or x.requires_grad):
+            raise NotImplementedError("uformer_amd.UNet has no autograd path yet: run it in eval() under torch.no_grad(), and train "
+                                      "the reference's UNet (INTEGRATION.md section A)")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()) and not getattr(self, "_warned_grad", False):
+            import warnings
+            warnings.warn("uformer_amd.UNet: eval() forward with grad mode on runs the inference kernels; the result has no grad_fn "
+                          "(wrap the call in torch.no_grad() to silence this)", stacklevel=2)
+            self._warned_grad = True
+        xin = x.detach().float().contiguous()
+        dt = ops.uf_dtype(self.compute_dtype)
+        with torch.cuda.device(x.device):
+            lib = _lib.load()
+            pk = self._get_packed(x.device)
+            need = lib.uf_unet_workspace_bytes(pk.desc, B, H, W, dt)
+            if need == 0:
+                raise UformerHipError("uf_unet_workspace_bytes: " + _lib.last_error())
+            ws = self._workspace(need, x.device)
+            out = torch.empty((B, 3, H, W), dtype=torch.float32, device=x.device)
+            _lib.check(lib.uf_unet_fwd(pk.desc, xin.data_ptr(), out.data_ptr(), B, H, W, dt, ws.data_ptr(), ws.numel(),
+                                       torch.cuda.current_stream().cuda_stream), "uf_unet_fwd")
+        return out.to(x.dtype)
+
+    def flops(self, H, W):
+        """model.py:176-200, the reference's count (multiply-accumulates)."""
+        d = self.dim
+        flops = 0
+        flops += self.ConvBlock1.flops(H, W)
+        flops += H / 2 * W / 2 * d * d * 4 * 4
+        flops += self.ConvBlock2.flops(H / 2, W / 2)
+        flops += H / 4 * W / 4 * d * 2 * d * 2 * 4 * 4
+        flops += self.ConvBlock3.flops(H / 4, W / 4)
+        flops += H / 8 * W / 8 * d * 4 * d * 4 * 4 * 4
+        flops += self.ConvBlock4.flops(H / 8, W / 8)
+        flops += H / 16 * W / 16 * d * 8 * d * 8 * 4 * 4
+        flops += self.ConvBlock5.flops(H / 16, W / 16)
+        flops += H / 8 * W / 8 * d * 16 * d * 8 * 2 * 2
+        flops += self.ConvBlock6.flops(H / 8, W / 8)
+        flops += H / 4 * W / 4 * d * 8 * d * 4 * 2 * 2
+        flops += self.ConvBlock7.flops(H / 4, W / 4)
+        flops += H / 2 * W / 2 * d * 4 * d * 2 * 2 * 2
+        flops += self.ConvBlock8.flops(H / 2, W / 2)
+        flops += H * W * d * 2 * d * 2 * 2
+        flops += self.ConvBlock9.flops(H, W)
+        flops += H * W * d * 3 * 3 * 3
+        return flops
+
+
+def get_arch(arch: str, train_ps: int = 128, dd_in: int = 3, embed_dim: int = 32, compute_dtype=torch.bfloat16) -> nn.Module:
     """utils/model_utils.py:56-81 ``get_arch(opt)`` with the option fields as arguments."""
     common = dict(win_size=8, token_projection='linear', token_mlp='leff', modulator=True, compute_dtype=compute_dtype)
     if arch == 'Uformer':
@@ -687,4 +827,6 @@ def get_arch(arch: str, train_ps: int = 128, dd_in: int = 3, embed_dim: int = 32
         return Uformer(img_size=train_ps, embed_dim=32, shift_flag=False, **common)
     if arch == 'Uformer_B':
         return Uformer(img_size=train_ps, embed_dim=32, depths=[1, 2, 8, 8, 2, 8, 8, 2, 1], dd_in=dd_in, **common)
+    if arch == 'UNet':
+        return UNet(dim=embed_dim, compute_dtype=compute_dtype)
     raise Exception("Arch error!")

@@ -206,3 +206,52 @@ class PackedModel:
             d.down_w_fm[k] = dwf.data_ptr() if dwf is not None else None
             self.keep.append((dw, db, uw, ub, dwf))
         self.desc = d
+
+
+def pack_conv(w: Tensor, dtype: torch.dtype) -> Tensor:
+    """Conv2d weight (Cout,Cin,k,k) -> T[Cout_p][k*k*Cin_p] with [n][(ky*k + kx)*Cin_p + c] = w[n][c][ky][kx], Cout_p = Cout rounded up
+    to 64, Cin_p = Cin rounded up to 32, zero padded (uf_conv_packed_elems, include/uformer_hip.h)."""
+    cout, cin, k, _ = w.shape
+    cp, np_ = (cin + 31) // 32 * 32, (cout + 63) // 64 * 64
+    t = torch.zeros(np_, k, k, cp, dtype=dtype, device=w.device)
+    t[:cout, :, :, :cin] = w.detach().permute(0, 2, 3, 1).to(dtype)
+    return t.reshape(np_, -1).contiguous()
+
+
+def pack_conv_dgrad(w: Tensor, dtype: torch.dtype) -> Tensor:
+    """The input gradient of a 3x3 stride-1 pad-1 conv is the same conv with the flipped, transposed weight w'[c][n][2-ky][2-kx]:
+    its pack_conv form, for uf_conv3x3_fwd's epilogue 3."""
+    return pack_conv(w.detach().transpose(0, 1).flip(2, 3), dtype)
+
+
+class PackedUNet:
+    """All packed weights of one ``UNet`` + the ``uf_unet_desc`` that points at them."""
+
+    def __init__(self, sd: Dict[str, Tensor], dim: int, dtype: torch.dtype):
+        f = lambda k: sd[k].detach().float().clone().contiguous()  # noqa: E731
+        d = _lib.UnetDesc()
+        d.dim = dim
+        keep: Dict[str, Tensor] = {
+            "in_w27": pack_input_proj(sd["ConvBlock1.block.0.weight"]), "in_b": f("ConvBlock1.block.0.bias"),
+            "c11_w1": sd["ConvBlock1.conv11.weight"].detach().float().reshape(dim, -1).clone().contiguous(),
+            "c11_b1": f("ConvBlock1.conv11.bias"),
+            "out_w": pack_output_proj(sd["conv10.weight"]), "out_b": f("conv10.bias"),
+        }
+        for name, tns in keep.items():
+            setattr(d, name, tns.data_ptr())
+        for i in range(9):
+            p = f"ConvBlock{i + 1}."
+            for slot, key in (("w2", "block.2"),) + ((("w0", "block.0"), ("w11", "conv11")) if i > 0 else ()):
+                w = keep[f"{slot}.{i}"] = pack_conv(sd[p + key + ".weight"], dtype)
+                b = keep[f"b{slot[1:]}.{i}"] = f(p + key + ".bias")
+                getattr(d, slot)[i] = w.data_ptr()
+                getattr(d, "b" + slot[1:])[i] = b.data_ptr()
+        for k in range(4):
+            w = keep[f"pool_w.{k}"] = pack_conv(sd[f"pool{k + 1}.weight"], dtype)
+            b = keep[f"pool_b.{k}"] = f(f"pool{k + 1}.bias")
+            d.pool_w[k], d.pool_b[k] = w.data_ptr(), b.data_ptr()
+            w = keep[f"up_w.{k}"] = pack_upsample(sd[f"upv{k + 6}.weight"], dtype)
+            b = keep[f"up_b.{k}"] = f(f"upv{k + 6}.bias")
+            d.up_w[k], d.up_b[k] = w.data_ptr(), b.data_ptr()
+        self.keep = keep
+        self.desc = d

@@ -178,8 +178,40 @@ def synth_state_dict(cfg: UformerConfig, seed: int = 1234) -> Dict[str, torch.Te
     does not depend on key order.  Biases, LN affine params and the relative-position
     tables are non-trivial so those code paths are exercised by the parity tests.
     """
+    return _synth(state_dict_spec(cfg), seed)
+
+
+def unet_state_dict_spec(dim: int = 32) -> List[Tuple[str, Tuple[int, ...], str]]:
+    """(key, shape, kind) of the reference's ``UNet(dim=dim)`` state_dict in its order (model.py:128-152)."""
+    spec: List[Tuple[str, Tuple[int, ...], str]] = []
+
+    def block(name, cin, cout):
+        spec.extend([(f"{name}.block.0.weight", (cout, cin, 3, 3), "conv_w"), (f"{name}.block.0.bias", (cout,), "conv_b"),
+                     (f"{name}.block.2.weight", (cout, cout, 3, 3), "conv_w"), (f"{name}.block.2.bias", (cout,), "conv_b"),
+                     (f"{name}.conv11.weight", (cout, cin, 1, 1), "conv_w"), (f"{name}.conv11.bias", (cout,), "conv_b")])
+
+    block("ConvBlock1", 3, dim)
+    for k in range(1, 5):
+        c = dim * 2 ** (k - 1)
+        spec.extend([(f"pool{k}.weight", (c, c, 4, 4), "conv_w"), (f"pool{k}.bias", (c,), "conv_b")])
+        block(f"ConvBlock{k + 1}", c, 2 * c)
+    for k in range(6, 10):
+        cout = dim * 2 ** (9 - k)
+        spec.extend([(f"upv{k}.weight", (2 * cout, cout, 2, 2), "deconv_w"), (f"upv{k}.bias", (cout,), "conv_b")])
+        block(f"ConvBlock{k}", 2 * cout, cout)
+    spec.extend([("conv10.weight", (3, dim, 3, 3), "conv_w"), ("conv10.bias", (3,), "conv_b")])
+    return spec
+
+
+def synth_unet_state_dict(dim: int = 32, seed: int = 1234) -> Dict[str, torch.Tensor]:
+    """Deterministic weights of ``UNet(dim)`` in the reference layout, drawn as ``synth_state_dict`` draws them (per-key seeding,
+    the conv_w / conv_b / deconv_w kinds)."""
+    return _synth(unet_state_dict_spec(dim), seed)
+
+
+def _synth(spec, seed: int) -> Dict[str, torch.Tensor]:
     out: Dict[str, torch.Tensor] = {}
-    for key, shape, kind in state_dict_spec(cfg):
+    for key, shape, kind in spec:
         h = int.from_bytes(hashlib.sha256(f"{seed}:{key}".encode()).digest()[:6], "little")
         g = torch.Generator().manual_seed(h)
         if kind == "rpi":
