@@ -95,7 +95,8 @@ int uf_linear_fwd(const void* A, const void* W, const float* bias, void* out, in
 /* ---- a7: fused Q/K/V projection (LinearProjection.forward, model.py:431-442) --------------
  * A T[M][C] window-order tokens; Wqkv T[3C][C] = cat(to_q.weight, to_kv.weight); bias f32[3C].
  * Writes q T[M/64][heads][64][hd] (already multiplied by hd^-0.5, model.py:497),
- *        k T[M/64][heads][64][hd],  vt T[M/64][heads][hd][64] (V transposed per window/head). */
+ *        k T[M/64][heads][64][hd],  vt T[M/64][heads][hd][64] (V transposed per window/head).  hd = C / heads in {16, 32, 64}
+ * (uf_ln_qkv_fwd likewise, C <= 512). */
 int uf_qkv_fwd(const void* A, const void* Wqkv, const float* bqkv, void* q, void* k, void* vt,
                int M, int C, int heads, uf_dtype dtype, void* stream);
 
@@ -117,7 +118,7 @@ int uf_ln_linear_gelu_fwd(const float* x, int ld, const float* gamma, const floa
  * relative_position_bias_table[relative_position_index] permuted (model.py:500-502).
  * shift>0 adds the SW-MSA mask analytically (window position from H,W);  mask (optional,
  * f32 [n_mask][64][64], row = window index % n_mask, model.py:508-512) is added on top.
- * out T[M][C], channel = head*hd + d (model.py:519). */
+ * out T[M][C], channel = head*hd + d (model.py:519).  head_dim 16, 32 or 64. */
 int uf_window_attention_fwd(const void* q, const void* k, const void* vt, const float* bias_dense,
                             const float* mask, int n_mask, void* out, int n_windows, int heads,
                             int head_dim, int H, int W, int shift, uf_dtype dtype, void* stream);
@@ -199,7 +200,9 @@ int uf_leff_fwd(const uf_block_params* p, float* x, int ld, int B, int H, int W,
 int uf_lewin_attn_train_fwd(const uf_block_params* p, const float* x, int ld, float* x1, int ld1, int B, int H, int W, int C,
                             const float* drop_attn, uf_dtype dtype, void* xn, void* q, void* k, void* vt, void* o, void* z, void* a1,
                             void* stream);
-/* whole block = the two halves */
+/* whole block = the two halves.  Blocks the fused kernels do not cover (head_dim 16 or 64, f32 at C = 512, a caller mask) run LN -> q|k|v^T ->
+ * attention -> projection as separate launches; C = 1024 (embed_dim 64) also runs the LeFF unfused and needs the larger workspace
+ * uf_block_workspace_bytes reports for it. */
 int uf_lewin_block_fwd(const uf_block_params* p, float* x, int ld, int B, int H, int W, int C,
                        const float* user_mask, int n_mask, uf_dtype dtype, void* ws,
                        size_t ws_bytes, void* stream);
@@ -289,7 +292,7 @@ int uf_linear_wgrad(const void* dY, int ldy, const void* X, int ldx, float* dW, 
  * operands of uf_window_attention_fwd: q (scaled), k T[n_windows*heads][64][hd], vt T[..][hd][64], bias_dense, mask.
  * dO T[n_windows*64][ldo] is the gradient of the merged-head output.  dq, dk, dvt: gradients wrt q (as stored, i.e.
  * scaled), k, vt, same layouts; dbias f32[heads][64][64] = dS summed over all windows (OVERWRITTEN; scatter-add it
- * through relative_position_index for the table gradient).  head_dim 32. */
+ * through relative_position_index for the table gradient).  head_dim 16, 32 or 64. */
 size_t uf_window_attention_bwd_workspace_bytes(int n_windows, int heads);
 int uf_window_attention_bwd(const void* q, const void* k, const void* vt, const float* bias_dense, const float* mask,
                             int n_mask, const void* dO, int ldo, void* dq, void* dk, void* dvt, float* dbias,

@@ -55,25 +55,31 @@ __global__ __launch_bounds__(256, 4) void window_attn_kernel(const T* __restrict
     const T* vp = vt + base;
 
     // ---- S^T = K Q^T ------------------------------------------------------------------
-    Frag<T> qf[4], kf[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (fg * 8 < HD) {
-            load_frag(qf[i], qp + (i * 16 + fr) * HD + fg * 8);
-            load_frag(kf[i], kp + (i * 16 + fr) * HD + fg * 8);
-        } else {  // head_dim 16: k-slots 16..31 are zero padding
-            qf[i].zero();
-            kf[i].zero();
-        }
-    }
+    // head_dim 64: two 32-wide k-steps, the fragments of one step live at a time (s[4][4] alone is 64 registers)
+    constexpr int KS = HD > 32 ? HD / 32 : 1;
     f32x4 s[4][4];  // [kt][qt]
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
-        for (int qt = 0; qt < 4; ++qt) {
-            s[kt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            mma16(s[kt][qt], kf[kt], qf[qt]);
+        for (int qt = 0; qt < 4; ++qt) s[kt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        Frag<T> qf[4], kf[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (fg * 8 < HD) {
+                load_frag(qf[i], qp + (i * 16 + fr) * HD + ks * 32 + fg * 8);
+                load_frag(kf[i], kp + (i * 16 + fr) * HD + ks * 32 + fg * 8);
+            } else {  // head_dim 16: k-slots 16..31 are zero padding
+                qf[i].zero();
+                kf[i].zero();
+            }
         }
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+            for (int qt = 0; qt < 4; ++qt) mma16(s[kt][qt], kf[kt], qf[qt]);
+    }
 
     // ---- + bias (+ masks) ---------------------------------------------------------------
     const int nWc = W >> 3, nW = (H >> 3) * nWc;
@@ -128,36 +134,40 @@ __global__ __launch_bounds__(256, 4) void window_attn_kernel(const T* __restrict
         inv[qt] = 1.0f / sum;
     }
 
-    // ---- O^T = V^T P^T -----------------------------------------------------------------------
-    f32x4 o[DT][4];
+    // ---- O^T = V^T P^T, normalise and store: out[(bw*64 + query)][h*HD + d] (model.py:519 head merge) ----------------
+    // head_dim 64: two passes of two d-tiles each, so that the output accumulators of a pass (32 registers) fit next to the
+    // 64 registers of P under the kernel's register bound; the P operands are rebuilt per pass (conversions only)
+    constexpr int DP = DT > 2 ? 2 : DT;  // d tiles per pass
+    const int C = heads * HD;
 #pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
+    for (int d0 = 0; d0 < DT; d0 += DP) {
+        f32x4 o[DP][4];
 #pragma unroll
-        for (int qt = 0; qt < 4; ++qt) o[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int dt = 0; dt < DP; ++dt)
 #pragma unroll
-    for (int sk = 0; sk < 2; ++sk) {  // 32 keys per step
-        Frag<T> vf[DT];
+            for (int qt = 0; qt < 4; ++qt) o[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-            const T* row = vp + (dt * 16 + fr) * 64 + sk * 32 + fg * 4;
-            load_vt(vf[dt], row, row + 16);
+        for (int sk = 0; sk < 2; ++sk) {  // 32 keys per step
+            Frag<T> vf[DP];
+#pragma unroll
+            for (int dt = 0; dt < DP; ++dt) {
+                const T* row = vp + ((d0 + dt) * 16 + fr) * 64 + sk * 32 + fg * 4;
+                load_vt(vf[dt], row, row + 16);
+            }
+#pragma unroll
+            for (int qt = 0; qt < 4; ++qt) {
+                Frag<T> pf;
+                PFrag<T>::make(pf, s[2 * sk][qt], s[2 * sk + 1][qt]);
+#pragma unroll
+                for (int dt = 0; dt < DP; ++dt) mma16(o[dt][qt], vf[dt], pf);
+            }
         }
 #pragma unroll
         for (int qt = 0; qt < 4; ++qt) {
-            Frag<T> pf;
-            PFrag<T>::make(pf, s[2 * sk][qt], s[2 * sk + 1][qt]);
+            T* orow = out + ((size_t)bw * 64 + qt * 16 + fr) * C + h * HD + fg * 4;
 #pragma unroll
-            for (int dt = 0; dt < DT; ++dt) mma16(o[dt][qt], vf[dt], pf);
+            for (int dt = 0; dt < DP; ++dt) store4(orow + (d0 + dt) * 16, o[dt][qt] * inv[qt]);
         }
-    }
-
-    // ---- normalise and store: out[(bw*64 + query)][h*HD + d] (model.py:519 head merge) --------
-    const int C = heads * HD;
-#pragma unroll
-    for (int qt = 0; qt < 4; ++qt) {
-        T* orow = out + ((size_t)bw * 64 + qt * 16 + fr) * C + h * HD + fg * 4;
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) store4(orow + dt * 16, o[dt][qt] * inv[qt]);
     }
 }
 
@@ -185,7 +195,7 @@ extern "C" int uf_window_attention_fwd(const void* q, const void* k, const void*
     using namespace uf;
     UF_REQUIRE(q && k && vt && bias_dense && out, UF_ERR_NULL, "uf_window_attention_fwd: null pointer");
     UF_REQUIRE(n_windows > 0 && heads > 0, UF_ERR_SHAPE, "uf_window_attention_fwd: n_windows=%d heads=%d", n_windows, heads);
-    UF_REQUIRE(head_dim == 16 || head_dim == 32, UF_ERR_UNSUPPORTED, "uf_window_attention_fwd: head_dim %d (16 or 32)", head_dim);
+    UF_REQUIRE(head_dim == 16 || head_dim == 32 || head_dim == 64, UF_ERR_UNSUPPORTED, "uf_window_attention_fwd: head_dim %d (16, 32 or 64)", head_dim);
     UF_REQUIRE(H % 8 == 0 && W % 8 == 0 && H >= 8 && W >= 8, UF_ERR_SHAPE, "uf_window_attention_fwd: H=%d W=%d", H, W);
     UF_REQUIRE(shift == 0 || shift == 4, UF_ERR_UNSUPPORTED, "uf_window_attention_fwd: shift %d (0 or 4)", shift);
     UF_REQUIRE(n_windows % ((H / 8) * (W / 8)) == 0, UF_ERR_SHAPE, "uf_window_attention_fwd: n_windows=%d not a multiple of nW", n_windows);
@@ -202,11 +212,11 @@ extern "C" int uf_window_attention_fwd(const void* q, const void* k, const void*
     hipLaunchKernelGGL((window_attn_kernel<TT, HDV>), grid, block, 0, st, (const TT*)q, (const TT*)k,            \
                        (const TT*)vt, bias_dense, mask, n_mask, (TT*)out, n_pairs, heads, H, W, shift)
     if (dtype == UF_BF16) {
-        if (head_dim == 32) UF_ATTN_LAUNCH(bf16, 32); else UF_ATTN_LAUNCH(bf16, 16);
+        if (head_dim == 64) UF_ATTN_LAUNCH(bf16, 64); else if (head_dim == 32) UF_ATTN_LAUNCH(bf16, 32); else UF_ATTN_LAUNCH(bf16, 16);
     } else if (dtype == UF_F16) {
-        if (head_dim == 32) UF_ATTN_LAUNCH(f16, 32); else UF_ATTN_LAUNCH(f16, 16);
+        if (head_dim == 64) UF_ATTN_LAUNCH(f16, 64); else if (head_dim == 32) UF_ATTN_LAUNCH(f16, 32); else UF_ATTN_LAUNCH(f16, 16);
     } else if (dtype == UF_F32) {
-        if (head_dim == 32) UF_ATTN_LAUNCH(float, 32); else UF_ATTN_LAUNCH(float, 16);
+        if (head_dim == 64) UF_ATTN_LAUNCH(float, 64); else if (head_dim == 32) UF_ATTN_LAUNCH(float, 32); else UF_ATTN_LAUNCH(float, 16);
     } else {
         set_error("uf_window_attention_fwd: unknown dtype %d", (int)dtype);
         return UF_ERR_UNSUPPORTED;

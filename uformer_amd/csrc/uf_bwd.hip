@@ -1265,13 +1265,16 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(const T* __restric
                                                               T* __restrict__ dvt, T* __restrict__ dqkv, float qscale, float* __restrict__ ws_bias, int n_windows,
                                                               int heads, int H, int W, int shift) {
     constexpr int SZ = sizeof(T), EP = 16 / SZ, NDT = HD / 16;
-    static_assert(HD == 16 || HD == 32, "head_dim 16 or 32");
-    constexpr int SD = 32 * SZ + 16, ST = 64 * SZ + 16;       // row strides: [token][32 d slots] tiles, [d or token][token] tiles
+    static_assert(HD == 16 || HD == 32 || HD == 64, "head_dim 16, 32 or 64");
+    constexpr int DS = HD > 32 ? HD : 32;                     // d slots of a token-major row = rows of a d-major tile (HD = 64: 64, two MFMA k-steps)
+    constexpr int SD = DS * SZ + 16, ST = 64 * SZ + 16;       // row strides: [token][DS d slots] tiles, [d or token][token] tiles
     constexpr int NPC = 64 * HD / EP;                         // 16-byte pieces per tile (HD = 32: 256 bf16 / 512 f32; HD = 16: half of that)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Qs = smem;                 char* Ks = Qs + 64 * SD;  char* Vs = Ks + 64 * SD;  char* Gs = Vs + 64 * SD;   // token-major
-    char* QT = Gs + 64 * SD;         char* KT = QT + 32 * ST;  char* GT = KT + 32 * ST;                              // d-major
-    char* Ps = GT + 32 * ST;         char* PT = Ps + 64 * ST;  char* Ds = PT + 64 * ST;  char* DT = Ds + 64 * ST;   // 64 x 64
+    char* QT = Gs + 64 * SD;         char* KT = QT + DS * ST;  char* GT = KT + DS * ST;                              // d-major
+    // 64 x 64.  HD = 64: the four tiles lie OVER the four token-major tiles (same size: SD == ST), which are dead once S and dP are in
+    // registers -- one more barrier per window instead of 68 KiB of LDS (f32 would not fit 160 KiB otherwise)
+    char* Ps = HD == 64 ? Qs : GT + DS * ST;  char* PT = Ps + 64 * ST;  char* Ds = PT + 64 * ST;  char* DT = Ds + 64 * ST;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fr = lane & 15, fg = lane >> 4;
     const int h = blockIdx.x;
@@ -1301,7 +1304,7 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(const T* __restric
 #pragma unroll
         for (int pc = tid; pc < NPC; pc += 256) {
             {
-                const int i = pc / (HD / EP), pp = pc % (HD / EP);           // token row, piece of the 32 d
+                const int i = pc / (HD / EP), pp = pc % (HD / EP);           // token row, piece of its HD d
                 float fq[EP], fk[EP], fgd[EP];
                 Vec<T>::load(q + base + i * HD + pp * EP, fq);
                 Vec<T>::load(k + base + i * HD + pp * EP, fk);
@@ -1326,20 +1329,27 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(const T* __restric
         }
         __syncthreads();
 
-        // ---- this wave's 16 query rows: S = q k^T and dP = dO v^T (one MFMA k-step: d = 32), then softmax algebra
-        Frag<T> aq, ag, bk[4], bv[4];
-        load_frag(aq, reinterpret_cast<const T*>(Qs + (i0 + fr) * SD) + fg * 8);
-        load_frag(ag, reinterpret_cast<const T*>(Gs + (i0 + fr) * SD) + fg * 8);
+        // ---- this wave's 16 query rows: S = q k^T and dP = dO v^T (one MFMA k-step per 32 d slots), then softmax algebra
         f32x4 sc[4], dp[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            load_frag(bk[t], reinterpret_cast<const T*>(Ks + (16 * t + fr) * SD) + fg * 8);
-            load_frag(bv[t], reinterpret_cast<const T*>(Vs + (16 * t + fr) * SD) + fg * 8);
             sc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
             dp[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-            mma16(sc[t], aq, bk[t]);       // D[row = 4fg + r -> query i0+4fg+r][col = fr -> key 16t+fr]
-            mma16(dp[t], ag, bv[t]);
         }
+#pragma unroll
+        for (int ks = 0; ks < DS / 32; ++ks) {
+            Frag<T> aq, ag, bk[4], bv[4];
+            load_frag(aq, reinterpret_cast<const T*>(Qs + (i0 + fr) * SD) + ks * 32 + fg * 8);
+            load_frag(ag, reinterpret_cast<const T*>(Gs + (i0 + fr) * SD) + ks * 32 + fg * 8);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                load_frag(bk[t], reinterpret_cast<const T*>(Ks + (16 * t + fr) * SD) + ks * 32 + fg * 8);
+                load_frag(bv[t], reinterpret_cast<const T*>(Vs + (16 * t + fr) * SD) + ks * 32 + fg * 8);
+                mma16(sc[t], aq, bk[t]);       // D[row = 4fg + r -> query i0+4fg+r][col = fr -> key 16t+fr]
+                mma16(dp[t], ag, bv[t]);
+            }
+        }
+        if constexpr (HD == 64) __syncthreads();   // every wave has read the token-major tiles: P / dS may overwrite them
         const int wi = bw % nW;
         const bool last_r = shift > 0 && (wi / nWc) == (H >> 3) - 1;
         const bool last_c = shift > 0 && (wi % nWc) == nWc - 1;
@@ -1383,7 +1393,7 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(const T* __restric
         __syncthreads();
 
         // ---- dq[i][d] = sum_j dS[i][j] k[j][d];  dk[j][d] = sum_i dS[i][j] q[i][d];  dv^T[d][j] = sum_i dO[i][d] P[i][j]
-        // wave w: 16-row tile w of dq and dk (both d tiles), 16-column tile w of dv^T (both d tiles); 64-long contraction
+        // wave w: 16-row tile w of dq and dk (all HD / 16 d tiles), 16-column tile w of dv^T (all d tiles); 64-long contraction
         f32x4 oq[NDT], ok[NDT], ov[NDT];
 #pragma unroll
         for (int c = 0; c < NDT; ++c) { oq[c] = f32x4{0.f, 0.f, 0.f, 0.f}; ok[c] = oq[c]; ov[c] = oq[c]; }
@@ -1406,7 +1416,7 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(const T* __restric
         }
         if (dqkv) {
             // merged form: the gradient of the fused q|k|v projection output, T[n_windows*64][3C] in window-row order, channel
-            // h*32 + d of each third; dq is multiplied by the query scale here (it is the gradient wrt the SCALED query, model.py:497)
+            // h*HD + d of each third; dq is multiplied by the query scale here (it is the gradient wrt the SCALED query, model.py:497)
             const int C3 = 3 * heads * HD;
             T* row0 = dqkv + (size_t)bw * 64 * C3 + h * HD;
 #pragma unroll
@@ -2037,7 +2047,7 @@ static int window_attention_bwd_any(const void* q, const void* k, const void* vt
     UF_REQUIRE(q && k && vt && bias_dense && dO && ((dq && dk && dvt) || dqkv) && dbias && ws, UF_ERR_NULL, "uf_window_attention_bwd: null pointer");
     UF_REQUIRE(dtype_ok(dtype), UF_ERR_UNSUPPORTED, "uf_window_attention_bwd: dtype %d", (int)dtype);
     UF_REQUIRE(n_windows > 0 && heads > 0, UF_ERR_SHAPE, "uf_window_attention_bwd: n_windows=%d heads=%d", n_windows, heads);
-    UF_REQUIRE(head_dim == 32 || head_dim == 16, UF_ERR_UNSUPPORTED, "uf_window_attention_bwd: head_dim %d (16 or 32)", head_dim);
+    UF_REQUIRE(head_dim == 64 || head_dim == 32 || head_dim == 16, UF_ERR_UNSUPPORTED, "uf_window_attention_bwd: head_dim %d (16, 32 or 64)", head_dim);
     UF_REQUIRE(H % 8 == 0 && W % 8 == 0 && H >= 8 && W >= 8 && n_windows % ((H / 8) * (W / 8)) == 0, UF_ERR_SHAPE,
                "uf_window_attention_bwd: H=%d W=%d n_windows=%d", H, W, n_windows);
     UF_REQUIRE(shift == 0 || shift == 4, UF_ERR_UNSUPPORTED, "uf_window_attention_bwd: shift %d (0 or 4)", shift);
@@ -2050,12 +2060,14 @@ static int window_attention_bwd_any(const void* q, const void* k, const void* vt
     const int G = attn_bwd_chunks(n_windows, heads);
     const float qscale = (float)(1.0 / sqrt((double)head_dim));   // python: head_dim ** -0.5, rounded once to f32
     const int SZ = (int)dtype_size(dtype);
-    const int smem = 4 * 64 * (32 * SZ + 16) + 3 * 32 * (64 * SZ + 16) + 4 * 64 * (64 * SZ + 16);
+    // head_dim 64: 64-slot tiles, and the four 64 x 64 tiles of P / dS share the LDS of the token-major operand tiles (119 KiB f32, 63 KiB for the 2-byte types)
+    const int DSL = head_dim == 64 ? 64 : 32;
+    const int smem = 4 * 64 * (DSL * SZ + 16) + 3 * DSL * (64 * SZ + 16) + (head_dim == 64 ? 0 : 4 * 64 * (64 * SZ + 16));
     char name[96] = "";
     if (timing_enabled()) snprintf(name, sizeof(name), "window_attn_bwd_%s %dx%d", dtype_name(dtype), n_windows, heads);
     {
         const double pairs = (double)n_windows * heads;
-        ScopedTimer tm(name, 2.0 * 5 * 64 * 64 * 32 * pairs, pairs * 64 * 32 * 7.0 * SZ, st);
+        ScopedTimer tm(name, 2.0 * 5 * 64 * 64 * DSL * pairs, pairs * 64 * DSL * 7.0 * SZ, st);
 #define UF_ATTN_BWD(TT, HDV)                                                                                                                        \
         {                                                                                                                                              \
             static bool done[64] = {};                                                                                                                \
@@ -2065,7 +2077,8 @@ static int window_attention_bwd_any(const void* q, const void* k, const void* vt
                                heads, H, W, shift);                                                                                                   \
         }
         // second version (accumulators chained into the operands, nothing stored transposed) for the 2-byte types (the first version serves f32)
-        const bool v2 = dtype_half(dtype) && ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)vt % 16) == 0 && ((uintptr_t)dO % 16) == 0;
+        // (head_dim 64 runs the first version for every type: the second one stages one 16-byte piece per thread and tile, which is a 32-slot row)
+        const bool v2 = head_dim != 64 && dtype_half(dtype) && ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)vt % 16) == 0 && ((uintptr_t)dO % 16) == 0;
 #define UF_ATTN_BWD2(TT, HDV)                                                                                                                       \
         if (mask) hipLaunchKernelGGL((window_attn_bwd2_kernel<TT, HDV, true>), dim3(heads, G), dim3(256), 0, st, (const TT*)q, (const TT*)k, (const TT*)vt, bias_dense, mask,      \
                            n_mask, (const TT*)dO, ldo, (TT*)dq, (TT*)dk, (TT*)dvt, (TT*)dqkv, qscale, (float*)ws, n_windows, heads, H, W, shift, pair);                      \
@@ -2075,7 +2088,7 @@ static int window_attention_bwd_any(const void* q, const void* k, const void* vt
         if (v2 && dtype == UF_BF16) { if (head_dim == 32) { UF_ATTN_BWD2(bf16, 32) } else { UF_ATTN_BWD2(bf16, 16) } }
         else if (v2) { if (head_dim == 32) { UF_ATTN_BWD2(f16, 32) } else { UF_ATTN_BWD2(f16, 16) } }
         else
-        UF_DISPATCH(dtype, TT, { if (head_dim == 32) UF_ATTN_BWD(TT, 32) else UF_ATTN_BWD(TT, 16) });
+        UF_DISPATCH(dtype, TT, { if (head_dim == 64) UF_ATTN_BWD(TT, 64) else if (head_dim == 32) UF_ATTN_BWD(TT, 32) else UF_ATTN_BWD(TT, 16) });
 #undef UF_ATTN_BWD2
 #undef UF_ATTN_BWD
     }

@@ -647,7 +647,33 @@ __global__ void pack_fm_kernel(const E* __restrict__ w, E* __restrict__ out, int
     for (int e = 0; e < 8; ++e) out[idx * 8 + e] = (k0 + e < K) ? w[(size_t)n * K + k0 + e] : E(0);
 }
 
+// the way back (K a multiple of 32): w[n][k0 .. k0+7] = one 8-element group of the fragment-major pack
+template <typename E>
+__global__ void unpack_fm_kernel(const E* __restrict__ fm, E* __restrict__ w, int N, int K, int KS) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;   // one 8-element group
+    if (idx >= (long long)(N / 16) * KS * 64) return;
+    const int lane = (int)(idx & 63), fr = lane & 15, fg = lane >> 4;
+    const long long blk = idx >> 6;
+    const int ks = (int)(blk % KS), nt = (int)(blk / KS);
+    const int n = nt * 16 + fr, k0 = ks * 32 + fg * 8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) w[(size_t)n * K + k0 + e] = fm[idx * 8 + e];
+}
+
 }  // namespace
+
+// fragment-major pack -> row-major T[N][K] (N % 16 == 0, K % 32 == 0): the blocks too wide for the kernels that stream the pack
+// (C = 1024) hand their weights to the row-major GEMM this way (uf_model.hip)
+int launch_unpack_weight_fm(const void* fm, void* w, int N, int K, uf_dtype dtype, hipStream_t st) {
+    UF_REQUIRE(fm && w, UF_ERR_NULL, "unpack_weight_fm: null pointer");
+    UF_REQUIRE(N > 0 && K > 0 && N % 16 == 0 && K % 32 == 0, UF_ERR_SHAPE, "unpack_weight_fm: N=%d (multiple of 16) K=%d (multiple of 32)", N, K);
+    const int KS = K / 32;
+    const long long groups = (long long)(N / 16) * KS * 64;
+    dim3 grid((unsigned)((groups + 255) / 256));
+    if (dtype_half(dtype)) hipLaunchKernelGGL(unpack_fm_kernel<uint16_t>, grid, dim3(256), 0, st, (const uint16_t*)fm, (uint16_t*)w, N, K, KS);
+    else hipLaunchKernelGGL(unpack_fm_kernel<uint32_t>, grid, dim3(256), 0, st, (const uint32_t*)fm, (uint32_t*)w, N, K, KS);
+    return check_launch("unpack_weight_fm");
+}
 
 int launch_layernorm(const float* x, int ld_x, const float* gamma, const float* beta, const float* modulator, void* out,
                      int rows, int H, int W, int C, int windowed, int shift, uf_dtype dtype, hipStream_t st) {

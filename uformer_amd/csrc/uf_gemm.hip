@@ -986,7 +986,7 @@ extern "C" int uf_qkv_fwd(const void* A, const void* Wqkv, const float* bqkv, vo
     UF_REQUIRE(q && k && vt, UF_ERR_NULL, "uf_qkv_fwd: null output");
     UF_REQUIRE(heads > 0 && C % heads == 0, UF_ERR_SHAPE, "uf_qkv_fwd: C=%d heads=%d", C, heads);
     const int hd = C / heads;
-    UF_REQUIRE(hd == 16 || hd == 32, UF_ERR_UNSUPPORTED, "uf_qkv_fwd: head_dim %d (16 or 32 supported)", hd);
+    UF_REQUIRE(hd == 16 || hd == 32 || hd == 64, UF_ERR_UNSUPPORTED, "uf_qkv_fwd: head_dim %d (16, 32 or 64 supported)", hd);
     UF_REQUIRE(M % 64 == 0, UF_ERR_SHAPE, "uf_qkv_fwd: M=%d is not a whole number of 64-token windows", M);
     uf::GemmParams p{};
     p.A = A; p.lda = C; p.W = Wqkv; p.bias = bqkv; p.M = M; p.N = 3 * C; p.K = C;

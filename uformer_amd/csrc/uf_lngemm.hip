@@ -402,7 +402,7 @@ extern "C" int uf_ln_qkv_fwd(const float* x, int ld, const float* gamma, const f
     UF_REQUIRE(q && k && vt, UF_ERR_NULL, "uf_ln_qkv_fwd: null output");
     UF_REQUIRE(heads > 0 && C % heads == 0, UF_ERR_SHAPE, "uf_ln_qkv_fwd: C=%d heads=%d", C, heads);
     const int hd = C / heads;
-    UF_REQUIRE(hd == 16 || hd == 32, UF_ERR_UNSUPPORTED, "uf_ln_qkv_fwd: head_dim %d (16 or 32 supported)", hd);
+    UF_REQUIRE(hd == 16 || hd == 32 || hd == 64, UF_ERR_UNSUPPORTED, "uf_ln_qkv_fwd: head_dim %d (16, 32 or 64 supported)", hd);
     UF_REQUIRE(shift >= 0 && shift < 8, UF_ERR_SHAPE, "uf_ln_qkv_fwd: shift=%d", shift);
     LnGemmParams p{};
     p.x = x; p.ld = ld; p.gamma = gamma; p.beta = beta; p.modulator = modulator; p.Wt = Wqkv; p.bias = bqkv;

@@ -14,17 +14,26 @@ namespace uf {
 int launch_layernorm(const float* x, int ld_x, const float* gamma, const float* beta, const float* modulator, void* out,
                      int rows, int H, int W, int C, int windowed, int shift, uf_dtype dtype, hipStream_t st);
 
+int launch_unpack_weight_fm(const void* fm, void* w, int N, int K, uf_dtype dtype, hipStream_t st);
+
 namespace {
 
 struct BlockWs {
     char* a;   // T[M][C]   : LN output / attention output
     char* h1;  // T[M][4C]  : q,k,v^T (first 3*M*C) / LeFF hidden after fc1
     char* h2;  // T[M][4C]  : LeFF hidden after the depthwise conv
+    char* wr;  // T[4C][C]  : one weight of the block in row-major form (wide blocks only, see wide_block)
 };
+
+// C = 1024 (the bottleneck and dec0 of an embed_dim-64 model): past the widths the pack-streaming kernels are built for (ln_gemm's [64][C]
+// operand tile and leff2's accumulators top out at C = 512).  Such a block runs LayerNorm, the row-major GEMM, the stencil and the
+// residual GEMM as separate launches; uf_block_params carries q|k|v, linear1 and linear2 in the fragment-major pack only, so each is
+// laid back out row-major into `wr` right before its GEMM (11 C^2 elements per block: ~1 % of the block's own traffic at 4096 tokens).
+bool wide_block(size_t C) { return C > 512; }
 
 size_t block_ws_bytes(size_t M, size_t C, uf_dtype dtype) {
     const size_t sz = dtype_size(dtype);
-    return align_up(M * C * sz, 256) + 2 * align_up(M * 4 * C * sz, 256);
+    return align_up(M * C * sz, 256) + 2 * align_up(M * 4 * C * sz, 256) + (wide_block(C) ? align_up(4 * C * C * sz, 256) : 0);
 }
 
 int carve(BlockWs& w, void* ws, size_t ws_bytes, size_t M, size_t C, uf_dtype dtype) {
@@ -36,6 +45,7 @@ int carve(BlockWs& w, void* ws, size_t ws_bytes, size_t M, size_t C, uf_dtype dt
     w.a = (char*)ws;
     w.h1 = w.a + align_up(M * C * sz, 256);
     w.h2 = w.h1 + align_up(M * 4 * C * sz, 256);
+    w.wr = w.h2 + align_up(M * 4 * C * sz, 256);
     return UF_OK;
 }
 
@@ -74,8 +84,17 @@ int attn_half(const uf_block_params* p, float* x, int ld, int B, int H, int W, i
     char* q = w.h1;
     char* k = q + (size_t)M * C * sz;
     char* vt = k + (size_t)M * C * sz;
-    int rc = uf_ln_qkv_fwd(x, ld, p->norm1_w, p->norm1_b, p->modulator, p->wqkv_fm, p->bqkv, q, k, vt, B, H, W, C, heads,
+    int rc;
+    if (wide_block(C)) {
+        rc = launch_layernorm(x, ld, p->norm1_w, p->norm1_b, p->modulator, w.a, M, H, W, C, 1, p->shift, dtype, st);
+        if (rc) return rc;
+        rc = launch_unpack_weight_fm(p->wqkv_fm, w.wr, 3 * C, C, dtype, st);
+        if (rc) return rc;
+        rc = uf_qkv_fwd(w.a, w.wr, p->bqkv, q, k, vt, M, C, heads, dtype, st);
+    } else {
+        rc = uf_ln_qkv_fwd(x, ld, p->norm1_w, p->norm1_b, p->modulator, p->wqkv_fm, p->bqkv, q, k, vt, B, H, W, C, heads,
                            p->shift, dtype, st);
+    }
     if (rc) return rc;
     // softmax(q k^T + bias + mask) v                    (model.py:498-519)
     rc = uf_window_attention_fwd(q, k, vt, p->rpb_dense, user_mask, n_mask, w.a, M / 64, heads, hd, H, W, p->shift, dtype, st);
@@ -91,6 +110,24 @@ int attn_half(const uf_block_params* p, float* x, int ld, int B, int H, int W, i
 int leff_half(const uf_block_params* p, float* x, int ld, int B, int H, int W, int C, uf_dtype dtype, const BlockWs& w,
               hipStream_t st, bool fc1_done = false, const float* drop = nullptr) {
     const int M = B * H * W;
+    if (wide_block(C)) {   // LN2, linear1 + GELU, depthwise 3x3 + GELU, linear2 + residual: four launches (model.py:987, :657-661, :674-683)
+        UF_REQUIRE(!drop && !fc1_done, UF_ERR_UNSUPPORTED, "leff: C=%d runs unfused, without DropPath scales", C);
+        int rc = launch_layernorm(x, ld, p->norm2_w, p->norm2_b, nullptr, w.a, M, H, W, C, 0, 0, dtype, st);
+        if (rc) return rc;
+        rc = launch_unpack_weight_fm(p->w1_fm, w.wr, 4 * C, C, dtype, st);
+        if (rc) return rc;
+        rc = uf_linear_fwd(w.a, w.wr, p->b1, w.h1, M, 4 * C, C, 1, dtype, st);
+        if (rc) return rc;
+        rc = uf_dwconv3x3_gelu_fwd(w.h1, p->wdw9, p->bdw, w.h2, B, H, W, 4 * C, dtype, st);
+        if (rc) return rc;
+        rc = launch_unpack_weight_fm(p->w2_fm, w.wr, C, 4 * C, dtype, st);
+        if (rc) return rc;
+        GemmParams g{};
+        g.A = w.h2; g.lda = 4 * C; g.W = w.wr; g.bias = p->b2; g.M = M; g.N = C; g.K = 4 * C;
+        g.H = H; g.W_ = W; g.hw = H * W;
+        g.out = x; g.ldo = ld; g.resid = x; g.ldr = ld;
+        return launch_gemm(g, A_PLAIN, E_RES, dtype, st);
+    }
     // LN2 -> linear1 -> GELU, one kernel                 (model.py:987, :657-658, :671) unless the attention kernel did it
     if (!fc1_done) {
         int rc = uf_ln_linear_gelu_fwd(x, ld, p->norm2_w, p->norm2_b, p->w1_fm, p->b1, w.h1, M, 4 * C, C, dtype, st);
@@ -260,10 +297,17 @@ int make_plan(Plan& pl, const uf_model_desc* d, int B, int H, int W, uf_dtype dt
 // slack so that the per-part plans of the multi-stream mode (every buffer 256-byte aligned) fit the workspace of the whole batch
 constexpr size_t WS_SPLIT_SLACK = 256 * 256;
 
+// Every part of the multi-stream mode carves its own row-major weight slot (wide blocks, block_ws_bytes): unlike the activations it does not
+// shrink with the part's batch, so the whole-batch plan (one slot) is topped up with one slot per possible side stream.
+static size_t ws_split_wide_extra(const uf_model_desc* d, uf_dtype dtype) {
+    const size_t C = (size_t)16 * d->embed_dim;
+    return wide_block(C) ? (size_t)MAX_SIDE * align_up(4 * C * C * dtype_size(dtype), 256) : 0;
+}
+
 extern "C" size_t uf_uformer_workspace_bytes(const uf_model_desc* d, int B, int H, int W, uf_dtype dtype) {
     Plan pl;
     if (make_plan(pl, d, B, H, W, dtype) != UF_OK) return 0;
-    return pl.total + WS_SPLIT_SLACK;
+    return pl.total + WS_SPLIT_SLACK + ws_split_wide_extra(d, dtype);
 }
 
 // bneck (NULL for the standard model): the uf_block4_params of the bottleneck's depths[4] blocks, which then run on the 4x4-window path
@@ -386,7 +430,7 @@ extern "C" int uf_uformer_fwd(const uf_model_desc* d, const float* img, float* o
 extern "C" size_t uf_uformer_win4_workspace_bytes(const uf_model_desc* d, int B, int H, int W, uf_dtype dtype) {
     Plan pl;
     if (make_plan(pl, d, B, H, W, dtype, 4) != UF_OK) return 0;
-    return pl.total + WS_SPLIT_SLACK;
+    return pl.total + WS_SPLIT_SLACK + ws_split_wide_extra(d, dtype);
 }
 
 extern "C" int uf_uformer_win4_fwd(const uf_model_desc* d, const uf_block4_params* bottleneck, const float* img, float* out, int B, int H, int W,

@@ -102,6 +102,8 @@ def arch_config(name: str, img_size: int = 256, dd_in: int = 3) -> UformerConfig
         return UformerConfig(img_size=img_size, embed_dim=16, depths=(1,) * 9, modulator=True)
     if name == "tiny32":  # smallest head_dim-32 model, used by the GPU parity tests
         return UformerConfig(img_size=img_size, embed_dim=32, depths=(1, 2, 2, 2, 2, 2, 2, 2, 1), modulator=True)
+    if name == "tiny64":  # tiny32's shape at twice the width: head_dim 64 at every stage, C = 1024 at the bottleneck and dec0
+        return UformerConfig(img_size=img_size, embed_dim=64, depths=(1, 2, 2, 2, 2, 2, 2, 2, 1), modulator=True)
     raise ValueError(f"unknown arch {name!r}")
 
 

@@ -519,8 +519,11 @@ def choose_recompute(cfg, B: int, H: int, device, W: Optional[int] = None) -> bo
 class UformerTape:
     """One forward of the whole model (model.py:1269-1305) that keeps what the reverse sweep reads, and that sweep.
     ``drop_scales``: None (eval semantics) or a (2 * n_blocks, B) tensor of DropPath scales in execution order.
-    ``recompute`` (default: on whenever the fused kernels cover the operand type): a block keeps only its input and rebuilds its
-    intermediates at the start of its backward; off: the op-by-op forward keeps them (the round-1 form, ~18x the memory)."""
+    ``recompute`` (default for the 2-byte operand types: chosen from the batch and the free memory, choose_recompute): a block keeps only
+    its input and rebuilds its intermediates at the start of its backward -- a head_dim-32 block through the fused kernels and the
+    block-level C backward, a head_dim-64 block by rerunning the op-by-op forward (the unfused pieces) before the op-level backward;
+    head_dim-16 and 4x4-window blocks keep their intermediates in both forms.  Off: the op-by-op forward keeps them everywhere (the
+    round-1 form, ~18x the memory)."""
 
     def __init__(self, sd: Dict[str, Tensor], cfg, dtype: torch.dtype = torch.float32, drop_scales: Optional[Tensor] = None,
                  recompute: Optional[bool] = None, on_stage_done=None):
@@ -545,12 +548,12 @@ class UformerTape:
         dims_ = cfg.stage_dims()
         for s_ in range(9):
             hd_ = dims_[s_] // max(1, cfg.num_heads[s_])
-            if dims_[s_] % cfg.num_heads[s_] or hd_ not in (16, 32) or dims_[s_] % 16:
-                raise ops.UformerHipError(f"training: stage {s_} has {dims_[s_]} channels over {cfg.num_heads[s_]} heads (head_dim {hd_}); supported: head_dim 16 or 32, "
+            if dims_[s_] % cfg.num_heads[s_] or hd_ not in (16, 32, 64) or dims_[s_] % 16:
+                raise ops.UformerHipError(f"training: stage {s_} has {dims_[s_]} channels over {cfg.num_heads[s_]} heads (head_dim {hd_}); supported: head_dim 16, 32 or 64, "
                                           f"channels a multiple of 16 (every get_arch architecture, utils/model_utils.py:56-81)")
-        if self.recompute and not any(dims_[s_] == 32 * cfg.num_heads[s_] for s_ in range(9)):
+        if self.recompute and not any(dims_[s_] in (32 * cfg.num_heads[s_], 64 * cfg.num_heads[s_]) for s_ in range(9)):
             import warnings
-            warnings.warn("the recompute form was selected (use_checkpoint=True, recompute=True, or chosen from the free memory), but no stage has head_dim 32 (the fused kernels the recompute form is built on): every block keeps its "
+            warnings.warn("the recompute form was selected (use_checkpoint=True, recompute=True, or chosen from the free memory), but no stage has head_dim 32 or 64 (the widths the recompute form is built for): every block keeps its "
                           "intermediates (memory ~18x the recompute form)", stacklevel=2)
         shifts = cfg.block_shifts()
         wins = self.wins = cfg.stage_windows()
@@ -573,7 +576,8 @@ class UformerTape:
                 prefix = f"{STAGES[s]}.blocks.{i}."
                 dr = self.drop[2 * bi:2 * bi + 2] if self.drop is not None else None
                 # the fused kernels (and the block-level C backward built on them) cover head_dim 32; a head_dim-16 block (Uformer_T,
-                # utils/model_utils.py:66-67) takes the op-by-op forward that keeps its intermediates and the op-level backward
+                # utils/model_utils.py:66-67) or head_dim-64 block (embed_dim 64) takes the op-by-op forward that keeps its intermediates and the
+                # op-level backward
                 # (a 4x4-window block -- the bottleneck of a model built for 64x64 patches -- keeps its intermediates in both forms)
                 fusable = self.recompute and C == 32 * cfg.num_heads[s] and wins[s] == 8
                 # uf_pack_block_train (5 launches) covers C % 32 == 0; its pack also serves the op-by-op form as tensor views
@@ -583,7 +587,15 @@ class UformerTape:
                 else:
                     pk = self.packs[prefix] = (NativeBlockPack(sd, prefix, cfg.num_heads[s], shifts[s][i], T) if native else
                                                BlockPack(sd, prefix, cfg.num_heads[s], shifts[s][i], T, fused=fusable or fused_attn_covers(T, C, cfg.num_heads[s])))
-                if fusable:                                                     # fused kernels; the block's input is all that is kept
+                # a head_dim-64 block in the recompute form: the op-by-op forward, of which only the block's input is kept; its backward
+                # reruns the same unfused pieces (need_y=False: up to the stencil) and differentiates them -- the same kernels on the same
+                # operands as the kept form, so the same bits
+                unfused_rc = self.recompute and C == 64 * cfg.num_heads[s] and wins[s] == 8
+                if unfused_rc:
+                    y, _ = lewin_block_forward(t.reshape(B, res[s][0] * res[s][1], C), sd, prefix, cfg.num_heads[s], shifts[s][i], T, dr, pk, hw=res[s])
+                    self.saved_blocks[s].append(dict(x=t, drop=dr, pk=pk, unfused=(prefix, cfg.num_heads[s], shifts[s][i], res[s])))
+                    t = y.reshape(-1, C)
+                elif fusable:                                                   # fused kernels; the block's input is all that is kept
                     y = ops.lewin_block_train_fwd(pk.fused, t, B, res[s][0], res[s][1], T, None if dr is None else dr[0], None if dr is None else dr[1])
                     self.saved_blocks[s].append(dict(x=t, drop=dr, pk=pk))
                     t = y
@@ -646,7 +658,13 @@ class UformerTape:
             dyT = None                                                            # T(d * s2 of the block about to run): from the previous block's LN1 backward
             while blocks:
                 sv = blocks.pop()                                                 # frees the block's saved input as the sweep passes it
-                if "x2" not in sv:                                                # only the block input was kept: recomputation + backward in one C call
+                if "unfused" in sv:                                               # head_dim 64: only the block input was kept; rerun the op-by-op forward, then the op-level backward
+                    prefix_, heads_, shift_, hw_ = sv["unfused"]
+                    _, sv2 = lewin_block_forward(sv["x"].reshape(B, hw_[0] * hw_[1], C), sd, prefix_, heads_, shift_, T, sv["drop"], sv["pk"], need_y=False, hw=hw_)
+                    d, gb = lewin_block_backward(sv2, d, None)
+                    dyT = None
+                    del sv2
+                elif "x2" not in sv:                                              # only the block input was kept: recomputation + backward in one C call
                     pk, dr = sv["pk"], sv["drop"]
                     dxb, gv = ops.lewin_block_bwd(pk.train_params, sv["x"], d.reshape(-1, C), None if dr is None else dr[0], None if dr is None else dr[1],
                                                   B, res[s][0], res[s][1], pk.heads, T, ws=self._block_ws(s))
