@@ -172,7 +172,8 @@ typedef struct uf_block_params {
     const void* w1_fm;      /* T (4C,C) fragment-major mlp.linear1.0.weight */
     const float* b1;        /* (4C) */
     const float* wdw9;      /* (9,4C) tap-major repack of mlp.dwconv.0.weight (4C,1,3,3) */
-    const float* bdw;       /* (4C) */
+    const float* bdw;       /* (4C).  wdw9 = bdw = NULL: an Mlp block (token_mlp 'ffn' / 'mlp', model.py:890-891): w1_fm / b1 / w2_fm / b2 are
+                               mlp.fc1 / mlp.fc2 and the FFN half is uf_ffn_fwd (C <= 512; wider returns UF_ERR_UNSUPPORTED) */
     const void* w2_fm;      /* T (C,4C) fragment-major mlp.linear2.0.weight */
     const float* b2;        /* (C) */
     int32_t shift;          /* 0 or 4, decided at construction (model.py:1030, :863-866) */
@@ -190,6 +191,16 @@ int uf_lewin_attn_fwd(const uf_block_params* p, float* x, int ld, int B, int H, 
 /* ---- a10/a11: FFN half (model.py:987): x = x + LeFF(LN2(x)) ; in place. */
 int uf_leff_fwd(const uf_block_params* p, float* x, int ld, int B, int H, int W, int C,
                 uf_dtype dtype, void* ws, size_t ws_bytes, void* stream);
+/* ---- Mlp feed-forward (reference Mlp, model.py:623-642, with the block's norm2 and residual, :987), one kernel, in place:
+ *   x[m] += scale[image of m] * ( GELU( LN2(x[m]) W1^T + b1 ) W2^T + b2 )
+ * x f32[M] rows of C channels (stride ld; columns [C, ld) are not touched); W1_fm / W2_fm fragment-major T (4C,C) / (C,4C); b1 f32[4C], b2 f32[C];
+ * scale f32[B] per-image DropPath scale or NULL (= 1).  C in {16,32,64,128,256,512}; M and the tokens per image M / B multiples of 64;
+ * all pointers 16-byte aligned.  The 4C-wide hidden activations stay on chip (rounded to T after the GELU, as a stored activation is). */
+int uf_ffn_fwd(float* x, int ld, const float* gamma, const float* beta, const void* W1_fm, const float* b1, const void* W2_fm,
+               const float* b2, const float* scale, int B, int M, int C, uf_dtype dtype, void* stream);
+/* the FFN half of an Mlp block (wdw9 = bdw = NULL): the sibling of uf_leff_fwd, same workspace */
+int uf_mlp_fwd(const uf_block_params* p, float* x, int ld, int B, int H, int W, int C, uf_dtype dtype, void* ws, size_t ws_bytes,
+               void* stream);
 /* ---- a15, training forward of the attention half + linear1 (round 6; 2-byte operands, head_dim 32): the fused window kernel of
  * uf_lewin_attn_fwd with SIDE STORES of every operand the backward reads, so that the kept-intermediates training forward
  * (train/train_denoise.py:180-184 over model.py:951-987, :657-658) is one launch instead of six:

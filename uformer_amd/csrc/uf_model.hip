@@ -49,8 +49,14 @@ int carve(BlockWs& w, void* ws, size_t ws_bytes, size_t M, size_t C, uf_dtype dt
     return UF_OK;
 }
 
+// A block built with token_mlp = 'ffn' / 'mlp' (reference Mlp, model.py:623-642) has no depthwise convolution: its descriptor carries
+// wdw9 = bdw = NULL, and w1_fm / b1 / w2_fm / b2 are fc1 / fc2.
+bool mlp_block(const uf_block_params* p) { return !p->wdw9 && !p->bdw; }
+
 int check_block_args(const uf_block_params* p, const float* x, int ld, int B, int H, int W, int C, uf_dtype dtype) {
     UF_REQUIRE(p && x, UF_ERR_NULL, "block: null pointer");
+    UF_REQUIRE(!p->wdw9 == !p->bdw, UF_ERR_NULL, "block: wdw9 and bdw must both be set (LeFF) or both be NULL (Mlp, token_mlp = 'ffn')");
+    UF_REQUIRE(!(mlp_block(p) && wide_block((size_t)C)), UF_ERR_UNSUPPORTED, "block: token_mlp = 'ffn' is built for C <= 512 (got C=%d)", C);
     UF_REQUIRE(dtype_ok(dtype), UF_ERR_UNSUPPORTED, "block: dtype %d", (int)dtype);
     UF_REQUIRE(B > 0 && H >= 8 && W >= 8 && H % 8 == 0 && W % 8 == 0, UF_ERR_SHAPE, "block: B=%d H=%d W=%d (H,W multiples of 8)", B, H, W);
     UF_REQUIRE(C >= 16 && C % 16 == 0 && ld >= C && ld % 4 == 0, UF_ERR_SHAPE, "block: C=%d ld=%d", C, ld);
@@ -74,7 +80,7 @@ int attn_half(const uf_block_params* p, float* x, int ld, int B, int H, int W, i
     // (Stages with fewer windows than CUs -- 4 ... 64 at small batches -- stay on the fused kernel too: the 3-kernel path, whose GEMMs tile over the
     // whole chip, measured slower at every batch size from 1 to 16: profiles/r03_unfuse.txt, profiles/r05_run5_unfuse.txt.)
     if (attn_block_supported(p, user_mask, dtype, C, heads)) {
-        const bool with_fc1 = fc1_done && dtype_half(dtype) && C >= 32;
+        const bool with_fc1 = fc1_done && dtype_half(dtype) && C >= 32 && !mlp_block(p);   // an Mlp block: no phase 3, uf_ffn_fwd follows
         if (fc1_done) *fc1_done = with_fc1;
         return launch_attn_block(p, x, ld, B, H, W, C, dtype, with_fc1 ? w.h1 : nullptr, st, drop);
     }
@@ -107,9 +113,37 @@ int attn_half(const uf_block_params* p, float* x, int ld, int B, int H, int W, i
     return launch_gemm(g, A_PLAIN, E_RES_WINREV, dtype, st);
 }
 
+// Widths at which the unfused pair (LN2 + fc1 + GELU GEMM writing h, then the residual GEMM) measured faster than uf_ffn_fwd by more
+// than the run-to-run spread (profiles/ffn_fwd.json): C = 512 with 2-byte operands (64-row tiles give the 4096 / 16384
+// tokens of Uformer-B's two C = 512 stages 64 / 256 workgroups, each streaming all 4 MiB of weights: 81 against 42 us, 101 against 86 us).
+// f32 at C = 512 is not measured and stays fused.
+bool ffn_prefers_unfused(uf_dtype dtype, int C) { return C == 512 && dtype_half(dtype); }
+
+// FFN half of an Mlp block (model.py:987 with Mlp): x += drop * (fc2(GELU(fc1(LN2(x))))).  One fused kernel; the unfused pair of existing
+// entry points stays reachable (UF_VARIANT="ffn=1", or a width listed above) where its row-major W2 fits the idle h2 slot (M >= C).
+int mlp_half(const uf_block_params* p, float* x, int ld, int B, int H, int W, int C, uf_dtype dtype, const BlockWs& w, hipStream_t st,
+             const float* drop) {
+    const int M = B * H * W;
+    UF_REQUIRE(p->norm2_w && p->norm2_b && p->w1_fm && p->b1 && p->w2_fm && p->b2, UF_ERR_NULL, "mlp: null parameter");
+    UF_REQUIRE(!wide_block(C), UF_ERR_UNSUPPORTED, "mlp: token_mlp = 'ffn' is built for C <= 512 (got C=%d)", C);
+    if ((variant("ffn", 0) == 1 || ffn_prefers_unfused(dtype, C)) && M >= C) {
+        int rc = uf_ln_linear_gelu_fwd(x, ld, p->norm2_w, p->norm2_b, p->w1_fm, p->b1, w.h1, M, 4 * C, C, dtype, st);
+        if (rc) return rc;
+        rc = launch_unpack_weight_fm(p->w2_fm, w.h2, C, 4 * C, dtype, st);
+        if (rc) return rc;
+        GemmParams g{};
+        g.A = w.h1; g.lda = 4 * C; g.W = w.h2; g.bias = p->b2; g.M = M; g.N = C; g.K = 4 * C;
+        g.H = H; g.W_ = W; g.hw = H * W; g.scale = drop;
+        g.out = x; g.ldo = ld; g.resid = x; g.ldr = ld;
+        return launch_gemm(g, A_PLAIN, E_RES, dtype, st);
+    }
+    return uf_ffn_fwd(x, ld, p->norm2_w, p->norm2_b, p->w1_fm, p->b1, p->w2_fm, p->b2, drop, B, M, C, dtype, st);
+}
+
 int leff_half(const uf_block_params* p, float* x, int ld, int B, int H, int W, int C, uf_dtype dtype, const BlockWs& w,
               hipStream_t st, bool fc1_done = false, const float* drop = nullptr) {
     const int M = B * H * W;
+    if (mlp_block(p)) return mlp_half(p, x, ld, B, H, W, C, dtype, w, st, drop);
     if (wide_block(C)) {   // LN2, linear1 + GELU, depthwise 3x3 + GELU, linear2 + residual: four launches (model.py:987, :657-661, :674-683)
         UF_REQUIRE(!drop && !fc1_done, UF_ERR_UNSUPPORTED, "leff: C=%d runs unfused, without DropPath scales", C);
         int rc = launch_layernorm(x, ld, p->norm2_w, p->norm2_b, nullptr, w.a, M, H, W, C, 0, 0, dtype, st);
@@ -174,6 +208,17 @@ extern "C" int uf_leff_fwd(const uf_block_params* p, float* x, int ld, int B, in
     rc = carve(w, ws, ws_bytes, (size_t)B * H * W, C, dtype);
     if (rc) return rc;
     return leff_half(p, x, ld, B, H, W, C, dtype, w, (hipStream_t)stream);
+}
+
+extern "C" int uf_mlp_fwd(const uf_block_params* p, float* x, int ld, int B, int H, int W, int C, uf_dtype dtype, void* ws,
+                          size_t ws_bytes, void* stream) {
+    int rc = check_block_args(p, x, ld, B, H, W, C, dtype);
+    if (rc) return rc;
+    UF_REQUIRE(mlp_block(p), UF_ERR_UNSUPPORTED, "uf_mlp_fwd: a LeFF block (wdw9 / bdw set): call uf_leff_fwd");
+    BlockWs w;
+    rc = carve(w, ws, ws_bytes, (size_t)B * H * W, C, dtype);
+    if (rc) return rc;
+    return mlp_half(p, x, ld, B, H, W, C, dtype, w, (hipStream_t)stream, nullptr);
 }
 
 extern "C" int uf_lewin_block_fwd(const uf_block_params* p, float* x, int ld, int B, int H, int W, int C,

@@ -346,6 +346,7 @@ extern "C" int uf_window4_reverse(const void* windows, void* out, int B, int H, 
 extern "C" int uf_lewin_block4_fwd(const uf_block4_params* p, float* x, int ld, int B, int H, int W, int C, const float* drop_attn,
                                    const float* drop_leff, uf_dtype dtype, void* ws, size_t ws_bytes, void* stream) {
     UF_REQUIRE(p && x && ws, UF_ERR_NULL, "uf_lewin_block4_fwd: null pointer");
+    UF_REQUIRE(p->wdw9 || p->bdw, UF_ERR_UNSUPPORTED, "uf_lewin_block4_fwd: a block without depthwise weights (token_mlp = 'ffn') is not built for 4x4 windows");
     UF_REQUIRE(p->norm1_w && p->norm1_b && p->norm2_w && p->norm2_b && p->rpb4 && p->wqkv && p->bqkv && p->wproj && p->bproj && p->w1 && p->b1 &&
                p->wdw9 && p->bdw && p->w2 && p->b2, UF_ERR_NULL, "uf_lewin_block4_fwd: null parameter");
     int rc = check_attn4("uf_lewin_block4_fwd", B, H, W, C, p->heads, 3 * C, dtype);

@@ -168,6 +168,35 @@ class LeFF(nn.Module):
         return H * W * self.dim * self.hidden_dim + H * W * self.hidden_dim * 9 + H * W * self.hidden_dim * self.dim
 
 
+class Mlp(nn.Module):
+    """model.py:623-651: fc1 -> GELU -> fc2, the block's feed-forward half under ``token_mlp='ffn'`` / ``'mlp'``.  Inside a block the
+    whole half (norm2, both Linears, the residual) is one ``uf_ffn_fwd`` launch; this stand-alone forward runs the two GEMMs."""
+
+    def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.):
+        super().__init__()
+        if act_layer is not nn.GELU or drop:
+            raise NotImplementedError("Mlp is built with GELU and drop=0 (every reference arch)")
+        out_features = out_features or in_features
+        hidden_features = hidden_features or in_features
+        self.fc1 = nn.Linear(in_features, hidden_features)
+        self.act = act_layer()
+        self.fc2 = nn.Linear(hidden_features, out_features)
+        self.drop = nn.Dropout(drop)
+        self.in_features = in_features
+        self.hidden_features = hidden_features
+        self.out_features = out_features
+
+    def forward(self, x: Tensor, compute_dtype=torch.float32, *, hw: HW = None) -> Tensor:
+        bs, L, c = x.shape
+        a = _to_compute(x.reshape(bs * L, c), compute_dtype)
+        h = ops.linear(a, _to_compute(self.fc1.weight, compute_dtype), self.fc1.bias.detach().float(), 1)
+        y = ops.linear(h, _to_compute(self.fc2.weight, compute_dtype), self.fc2.bias.detach().float(), 0)
+        return y.reshape(bs, L, self.out_features).to(x.dtype)
+
+    def flops(self, H, W):
+        return H * W * self.in_features * self.hidden_features + H * W * self.hidden_features * self.out_features
+
+
 class Downsample(nn.Module):
     """model.py:730-753."""
 
@@ -251,7 +280,7 @@ class OutputProj(nn.Module):
 
 
 class LeWinTransformerBlock(nn.Module):
-    """model.py:850-1008 (``token_mlp='leff'``, no cross-modulator)."""
+    """model.py:850-1008 (``token_mlp`` 'leff', or 'ffn' / 'mlp' for the reference's Mlp; no cross-modulator)."""
 
     def __init__(self, dim, input_resolution, num_heads, win_size=8, shift_size=0, mlp_ratio=4., qkv_bias=True,
                  qk_scale=None, drop=0., attn_drop=0., drop_path=0., act_layer=nn.GELU, norm_layer=nn.LayerNorm,
@@ -259,8 +288,9 @@ class LeWinTransformerBlock(nn.Module):
         super().__init__()
         if cross_modulator:
             raise NotImplementedError("cross_modulator is never enabled by get_arch (SURVEY.md section 2 row 10)")
-        if token_mlp != 'leff':
-            raise NotImplementedError("only token_mlp='leff' is on the hot path (utils/model_utils.py:65-78)")
+        if token_mlp not in ('leff', 'ffn', 'mlp'):
+            raise NotImplementedError(f"token_mlp={token_mlp!r}: 'leff' and 'ffn' / 'mlp' are built ('fastleff' needs a third-party CUDA package, "
+                                      "model.py:895-896)")
         if norm_layer is not nn.LayerNorm or drop:
             raise NotImplementedError("LayerNorm / drop=0 only")
         self.dim = dim
@@ -288,7 +318,13 @@ class LeWinTransformerBlock(nn.Module):
                                     qk_scale=qk_scale, attn_drop=attn_drop, proj_drop=drop, token_projection=token_projection)
         self.drop_path_rate = float(drop_path)
         self.norm2 = norm_layer(dim)
-        self.mlp = LeFF(dim, int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
+        if token_mlp == 'leff':
+            self.mlp = LeFF(dim, int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
+        else:                                   # model.py:890-891
+            if self.win_size == 4 or dim > 512 or dim not in (16, 32, 64, 128, 256, 512):
+                raise NotImplementedError(f"token_mlp={token_mlp!r} is built for 8x8-window blocks of width 16 ... 512 (uf_ffn_fwd); this block has "
+                                          f"width {dim} and window {self.win_size} (img_size 64 and embed_dim 64 take token_mlp='leff' only)")
+            self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
         self._packed = None
 
     def extra_repr(self) -> str:
@@ -417,7 +453,7 @@ class Uformer(nn.Module):
         self.compute_dtype = compute_dtype
         self.cfg = UformerConfig(img_size=img_size, in_chans=in_chans, dd_in=dd_in, embed_dim=embed_dim,
                                  depths=tuple(depths), num_heads=tuple(num_heads), win_size=win_size, mlp_ratio=mlp_ratio,
-                                 modulator=modulator, shift_flag=shift_flag)
+                                 modulator=modulator, shift_flag=shift_flag, token_mlp=token_mlp)
         bad = self.cfg.unsupported_clamp() if win_size == 8 else None
         if bad is not None:       # model.py:863-866 clamps a stage's window to its resolution; built: 8, and 4 for the bottleneck alone
             s_, res_, win_ = bad
@@ -664,7 +700,8 @@ class Uformer(nn.Module):
         wins = self.cfg.stage_windows()
         for s in range(9):
             L = (r // div[s]) ** 2
-            total += self.cfg.depths[s] * L * dims[s] * (12 * dims[s] + 2 * wins[s] ** 2 + 36)
+            # LeFF: the depthwise conv's 9 taps over 4C channels (36); Mlp has none (model.py:644-651)
+            total += self.cfg.depths[s] * L * dims[s] * (12 * dims[s] + 2 * wins[s] ** 2 + (0 if self.cfg.mlp_is_ffn() else 36))
         for s in range(4):
             L = (r // div[s]) ** 2
             total += (L // 4) * dims[s] * 2 * dims[s] * 16

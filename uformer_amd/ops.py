@@ -288,6 +288,27 @@ def ln_linear_gelu(x: Tensor, gamma: Tensor, beta: Tensor, w1: Tensor, b1: Tenso
     return out
 
 
+def ffn(x: Tensor, gamma: Tensor, beta: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, scale: Optional[Tensor] = None, B: int = 1,
+        C: Optional[int] = None) -> Tensor:
+    """The fused Mlp half of a block, IN PLACE on ``x``: x[m, :C] += scale[image of m] * (GELU(LN2(x[m, :C]) w1^T + b1) w2^T + b2)  (model.py:623-642,
+    :987; uf_ffn_fwd).  x f32 (M, ld) contiguous rows on the GPU with the channels in columns [0, C) (``C`` default: ld); w1 T (4C, C), w2 T (C, 4C)
+    row-major (packed fragment-major here); scale f32 (B,) per-image DropPath scales or None.  Returns x."""
+    _dev(x, gamma, beta, w1, b1, w2, b2, scale)
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() != 2:
+        raise UformerHipError("ffn: x must be a contiguous f32 (M, ld) tensor (it is updated in place)")
+    dt = uf_dtype(w1.dtype)
+    M, ld = x.shape
+    Cc = ld if C is None else int(C)
+    if tuple(w1.shape) != (4 * Cc, Cc) or tuple(w2.shape) != (Cc, 4 * Cc):
+        raise UformerHipError(f"ffn: w1 {tuple(w1.shape)} / w2 {tuple(w2.shape)} do not match C = {Cc}")
+    keep = (_c(gamma, torch.float32), _c(beta, torch.float32), _pack_frag(w1), _c(b1, torch.float32), _pack_frag(_c(w2, w1.dtype)), _c(b2, torch.float32),
+            None if scale is None else _c(scale, torch.float32))
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().uf_ffn_fwd(_ptr(x), ld, _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), _ptr(keep[3]), _ptr(keep[4]), _ptr(keep[5]),
+                                          _ptr(keep[6]), B, M, Cc, dt, _stream()), "uf_ffn_fwd")
+    return x
+
+
 def window_attention_core(q: Tensor, k: Tensor, vt: Tensor, bias_dense: Tensor, *, H: int, W: int, shift: int = 0,
                           mask: Optional[Tensor] = None) -> Tensor:
     """softmax(q k^T + bias + masks) v -> (n_windows*64, C).  model.py:498-519."""

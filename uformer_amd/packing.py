@@ -108,10 +108,14 @@ def pack_block(sd: Dict[str, Tensor], prefix: str, heads: int, shift: int, dtype
         "bqkv": torch.cat([sd[prefix + "attn.qkv.to_q.bias"].detach(), sd[prefix + "attn.qkv.to_kv.bias"].detach()], 0).contiguous().float(),
         "wproj": t("attn.proj.weight"), "wproj_fm": pack_frag(sd[prefix + "attn.proj.weight"], dtype), "bproj": f("attn.proj.bias"),
         "norm2_w": f("norm2.weight"), "norm2_b": f("norm2.bias"),
-        "w1_fm": pack_frag(sd[prefix + "mlp.linear1.0.weight"], dtype), "b1": f("mlp.linear1.0.bias"),
-        "wdw9": pack_dwconv(sd[prefix + "mlp.dwconv.0.weight"]), "bdw": f("mlp.dwconv.0.bias"),
-        "w2_fm": pack_frag(sd[prefix + "mlp.linear2.0.weight"], dtype), "b2": f("mlp.linear2.0.bias"),
     }
+    if (prefix + "mlp.fc1.weight") in sd:      # Mlp (token_mlp 'ffn' / 'mlp'): fc1 / fc2 in the linear1 / linear2 slots, wdw9 = bdw = NULL (uf_ffn_fwd)
+        keep.update({"w1_fm": pack_frag(sd[prefix + "mlp.fc1.weight"], dtype), "b1": f("mlp.fc1.bias"),
+                     "w2_fm": pack_frag(sd[prefix + "mlp.fc2.weight"], dtype), "b2": f("mlp.fc2.bias")})
+    else:
+        keep.update({"w1_fm": pack_frag(sd[prefix + "mlp.linear1.0.weight"], dtype), "b1": f("mlp.linear1.0.bias"),
+                     "wdw9": pack_dwconv(sd[prefix + "mlp.dwconv.0.weight"]), "bdw": f("mlp.dwconv.0.bias"),
+                     "w2_fm": pack_frag(sd[prefix + "mlp.linear2.0.weight"], dtype), "b2": f("mlp.linear2.0.bias")})
     if (prefix + "modulator.weight") in sd:
         keep["modulator"] = f("modulator.weight")
     tab = pack_rpb_table(dense)
@@ -129,6 +133,8 @@ def pack_block(sd: Dict[str, Tensor], prefix: str, heads: int, shift: int, dtype
 
 def pack_block4(sd: Dict[str, Tensor], prefix: str, heads: int, dtype: torch.dtype):
     """``uf_block4_params`` of a 4x4-window block (row-major T weights, the (heads, 49) bias table): returns (Block4Params, keepalive)."""
+    if (prefix + "mlp.fc1.weight") in sd:
+        raise NotImplementedError("token_mlp='ffn' is not built for 4x4-window blocks (the bottleneck of an img_size-64 model)")
     if (prefix + "modulator.weight") in sd:
         raise NotImplementedError("a 4x4-window block with a modulator: the reference adds a (64, C) embedding to 16-token windows, "
                                   "which does not broadcast (model.py:868-869, :967-969)")

@@ -32,6 +32,10 @@ class UformerConfig:
     mlp_ratio: float = 4.0
     modulator: bool = False
     shift_flag: bool = True
+    token_mlp: str = "leff"      # 'leff' (LeFF) or 'ffn' / 'mlp' (Mlp: fc1 -> GELU -> fc2, model.py:890-893)
+
+    def mlp_is_ffn(self) -> bool:
+        return self.token_mlp in ("ffn", "mlp")
 
     # ---- geometry -------------------------------------------------------------------
     def stage_dims(self) -> List[int]:
@@ -109,9 +113,10 @@ def arch_config(name: str, img_size: int = 256, dd_in: int = 3) -> UformerConfig
 
 # ---- state_dict layout ------------------------------------------------------------------
 def block_spec(prefix: str, C: int, heads: int, win: int, modulator: bool,
-               mlp_ratio: float = 4.0, mod_win: int = None) -> Iterator[Tuple[str, Tuple[int, ...], str]]:
+               mlp_ratio: float = 4.0, mod_win: int = None, token_mlp: str = "leff") -> Iterator[Tuple[str, Tuple[int, ...], str]]:
     """(key, shape, kind) of one LeWinTransformerBlock, in registration order.  ``win``: the block's (clamped) window;
-    ``mod_win`` (default ``win``): the unclamped window the modulator embedding is sized by (model.py:868-869)."""
+    ``mod_win`` (default ``win``): the unclamped window the modulator embedding is sized by (model.py:868-869);
+    ``token_mlp``: 'leff', or 'ffn' / 'mlp' for the reference's Mlp (``mlp.fc1`` / ``mlp.fc2``, model.py:623-631)."""
     hid = int(C * mlp_ratio)
     if modulator:
         mw = win if mod_win is None else mod_win
@@ -128,6 +133,12 @@ def block_spec(prefix: str, C: int, heads: int, win: int, modulator: bool,
     yield prefix + "attn.proj.bias", (C,), "linear_b"
     yield prefix + "norm2.weight", (C,), "ln_w"
     yield prefix + "norm2.bias", (C,), "ln_b"
+    if token_mlp in ("ffn", "mlp"):
+        yield prefix + "mlp.fc1.weight", (hid, C), "linear_w"
+        yield prefix + "mlp.fc1.bias", (hid,), "linear_b"
+        yield prefix + "mlp.fc2.weight", (C, hid), "linear_w"
+        yield prefix + "mlp.fc2.bias", (C,), "linear_b"
+        return
     yield prefix + "mlp.linear1.0.weight", (hid, C), "linear_w"
     yield prefix + "mlp.linear1.0.bias", (hid,), "linear_b"
     yield prefix + "mlp.dwconv.0.weight", (hid, 1, 3, 3), "conv_w"
@@ -150,7 +161,7 @@ def state_dict_spec(cfg: UformerConfig) -> List[Tuple[str, Tuple[int, ...], str]
     def stage(s: int):
         for i in range(cfg.depths[s]):
             spec.extend(block_spec(f"{STAGES[s]}.blocks.{i}.", dims[s], cfg.num_heads[s],
-                                   wins[s], cfg.stage_has_modulator(s), cfg.mlp_ratio, mod_win=cfg.win_size))
+                                   wins[s], cfg.stage_has_modulator(s), cfg.mlp_ratio, mod_win=cfg.win_size, token_mlp=cfg.token_mlp))
 
     for s in range(4):
         stage(s)

@@ -62,12 +62,16 @@ class BlockPack:
         self.mod = f("modulator.weight") if (prefix + "modulator.weight") in p else None
         self.wqkv = torch.cat([f("attn.qkv.to_q.weight"), f("attn.qkv.to_kv.weight")], 0).to(T)
         self.bqkv = torch.cat([f("attn.qkv.to_q.bias"), f("attn.qkv.to_kv.bias")], 0)
-        self.wp, self.w1, self.w2 = f("attn.proj.weight").to(T), f("mlp.linear1.0.weight").to(T), f("mlp.linear2.0.weight").to(T)
+        self.mlp = block_is_mlp(p, prefix)      # Mlp (token_mlp 'ffn' / 'mlp'): fc1 / fc2, no depthwise taps
+        k1, k2 = ("mlp.fc1.weight", "mlp.fc2.weight") if self.mlp else ("mlp.linear1.0.weight", "mlp.linear2.0.weight")
+        self.wp, self.w1, self.w2 = f("attn.proj.weight").to(T), f(k1).to(T), f(k2).to(T)
         self.wqkv_t, self.wp_t, self.w1_t, self.w2_t = (w.t().contiguous() for w in (self.wqkv, self.wp, self.w1, self.w2))
-        self.w9 = packing.pack_dwconv(f("mlp.dwconv.0.weight"))
-        if T in (torch.bfloat16, torch.float16):
-            self.w9 = self.w9.to(T).float()          # taps rounded to the operand type, as the fused forward's matrix-pipe stencil and uf_pack_block_train do (round 6)
-        self.w9_flip = self.w9.flip(0).contiguous()
+        self.w9 = self.w9_flip = None
+        if not self.mlp:
+            self.w9 = packing.pack_dwconv(f("mlp.dwconv.0.weight"))
+            if T in (torch.bfloat16, torch.float16):
+                self.w9 = self.w9.to(T).float()          # taps rounded to the operand type, as the fused forward's matrix-pipe stencil and uf_pack_block_train do (round 6)
+            self.w9_flip = self.w9.flip(0).contiguous()
         self.bias = packing.rpb_dense(f("attn.relative_position_bias_table"), f("attn.relative_position_index"))
         self.p = p
         self.fused = None
@@ -206,6 +210,11 @@ def block_window(p: Dict[str, Tensor], prefix: str = "") -> int:
     return win
 
 
+def block_is_mlp(p: Dict[str, Tensor], prefix: str = "") -> bool:
+    """The block's feed-forward half is the reference's Mlp (token_mlp 'ffn' / 'mlp', model.py:890-891), told by its parameter names."""
+    return (prefix + "mlp.fc1.weight") in p
+
+
 def block_hw(L: int, hw: Optional[Tuple[int, int]], who: str = "LeWin block") -> Tuple[int, int]:
     """(H, W) of a (B, L, C) token map: ``hw`` when given (checked against L), else the square side the reference takes
     (model.py:910-911).  A non-square L without ``hw`` is an error, not a guess."""
@@ -262,6 +271,19 @@ def lewin_block_forward(x: Tensor, p: Dict[str, Tensor], prefix: str, heads: int
         # x + DropPath(window_reverse(proj(o))): the residual add, the scale and the un-partition in the projection GEMM's store   model.py:975-986
         x1 = ops.linear_residual(o, pk.wp, f("attn.proj.bias"), x2, s1, B, H, W, windowed=True, shift=shift)
         z = ops.layernorm(x1, f("norm2.weight"), f("norm2.bias"), B=B, H=H, W=W, dtype=T)
+    if block_is_mlp(p, prefix):
+        # Mlp: y = x1 + DropPath(fc2(GELU(fc1(z)))) (model.py:636-642, :987).  Only the pre-activation a1 is kept: the backward recomputes
+        # T(GELU(a1)) for fc2's weight gradient in one elementwise pass (uf_gelu_fwd) instead of storing 4C more channels per token.
+        if win == 4:
+            raise NotImplementedError("token_mlp='ffn' is not built for 4x4-window blocks")
+        if not fused_attn:
+            a1 = ops.linear(z, pk.w1, f("mlp.fc1.bias"))
+        y = None
+        if need_y:
+            y = ops.linear_residual(ops.gelu(a1), pk.w2, f("mlp.fc2.bias"), x1, s2, B, H, W).reshape(B, L, C)
+        saved = dict(s1=s1, s2=s2, p=p, prefix=prefix, heads=heads, shift=shift, T=T, shape=(B, L, C), hw=(H, W), x2=x2, xn=xn, q=q, k=k, vt=vt, o=o, x1=x1, z=z, a1=a1,
+                     h1=None, c=None, g2=None, pk=pk, mod=pk.mod is not None, win=win, qkv=qkv, mlp=True)
+        return y, saved
     if fused_attn or _GELU_IN:     # linear1 keeps only its pre-activation (the backward needs that one); the stencil activates it as it loads it
         if not fused_attn:
             a1 = ops.linear(z, pk.w1, f("mlp.linear1.0.bias"))
@@ -346,6 +368,8 @@ def lewin_block_backward(sv: Saved, dy: Tensor, dyT: Optional[Tensor] = None, ne
     dyf = dy.reshape(M, C).float()
     if dyT is None:
         _, dyT = ops.grad_fork(dyf, None, sv["s2"], B, H, W, T)              # gradient entering the (scaled) LeFF branch, as a GEMM operand
+    if sv.get("mlp"):
+        return _mlp_block_backward(sv, dyf, dyT, next_scale, side, g)
     # LeFF: linear2 -> GELU -> depthwise -> GELU -> linear1                                   (model.py:666-685)
     g[prefix + "mlp.linear2.0.weight"], g[prefix + "mlp.linear2.0.bias"] = side.run(lambda: ops.linear_wgrad(dyT, sv["g2"]))
     pk: BlockPack = sv["pk"]
@@ -418,6 +442,49 @@ def lewin_block_backward(sv: Saved, dy: Tensor, dyT: Optional[Tensor] = None, ne
     side.join()
     if next_scale is not _NO_CAST:
         return dx.reshape(B, L, C), g, None
+    return dx.reshape(B, L, C), g
+
+
+def _mlp_block_backward(sv: Saved, dyf: Tensor, dyT: Tensor, next_scale, side: "_Side", g: Grads):
+    """lewin_block_backward for a block whose feed-forward half is the reference's Mlp: fc2 -> GELU -> fc1 (model.py:636-642), then the
+    8x8-window attention half exactly as for a LeFF block.  Composed from the entry points the LeFF tape uses: uf_linear_wgrad, the
+    input-gradient GEMM with the GELU' epilogue (uf_linear_mul_dgelu), the fused LayerNorm backward."""
+    p, prefix, heads, shift, T = sv["p"], sv["prefix"], sv["heads"], sv["shift"], sv["T"]
+    B, L, C = sv["shape"]
+    H, W = sv["hw"]
+    M = B * L
+    f = lambda k: p[prefix + k]                                             # noqa: E731
+    pk: BlockPack = sv["pk"]
+    h = ops.gelu(sv["a1"])                                                  # T(GELU(a1)), recomputed: what fc2 read in the forward
+    g[prefix + "mlp.fc2.weight"], g[prefix + "mlp.fc2.bias"] = side.run(lambda: ops.linear_wgrad(dyT, h))
+    da1 = ops.linear_mul_dgelu(dyT, pk.w2_t, _zeros(4 * C, dyT.device), sv["a1"])       # dY W2, times GELU'(a1)
+    g[prefix + "mlp.fc1.weight"], g[prefix + "mlp.fc1.bias"] = side.run(lambda: ops.linear_wgrad(da1, sv["z"]))
+    dz = _input_grad(da1, pk.w1_t)
+    if _FUSE_FORK and dz.dtype == T:
+        dx1, g[prefix + "norm2.weight"], g[prefix + "norm2.bias"], dyw = ops.layernorm_bwd_fused(sv["x1"], f("norm2.weight"), dz, B, H, W, add=dyf,
+                                                                                                 cast=dict(scale=sv["s1"], windowed=True, shift=shift))
+    else:
+        dx1, g[prefix + "norm2.weight"], g[prefix + "norm2.bias"] = ops.layernorm_bwd_fused(sv["x1"], f("norm2.weight"), dz, B, H, W)
+        dx1, dyw = ops.grad_fork(dx1, dyf, sv["s1"], B, H, W, T, windowed=True, shift=shift, want_sum=True)
+    g[prefix + "attn.proj.weight"], g[prefix + "attn.proj.bias"] = side.run(lambda: ops.linear_wgrad(dyw, sv["o"]))
+    do = _input_grad(dyw, pk.wp_t)
+    dqkv, dbias = ops.window_attention_bwd_qkv(sv["q"], sv["k"], sv["vt"], pk.bias, do, H, W, shift)
+    g[prefix + "attn.relative_position_bias_table"] = side.run(lambda: ops.rpb_table_grad(dbias))
+    dWqkv, dbqkv = side.run(lambda: ops.linear_wgrad(dqkv, sv["xn"]))
+    g[prefix + "attn.qkv.to_q.weight"], g[prefix + "attn.qkv.to_kv.weight"] = dWqkv[:C], dWqkv[C:]
+    g[prefix + "attn.qkv.to_q.bias"], g[prefix + "attn.qkv.to_kv.bias"] = dbqkv[:C], dbqkv[C:]
+    dxn = _input_grad(dqkv, pk.wqkv_t)
+    if sv["mod"]:
+        g[prefix + "modulator.weight"] = side.run(lambda: ops.rows_sum(dxn.reshape(M // 64, 64 * C)).reshape(64, C))
+    dyT_next = None
+    if next_scale is not _NO_CAST and _FUSE_FORK and dxn.dtype == T:
+        dx, g[prefix + "norm1.weight"], g[prefix + "norm1.bias"], dyT_next = ops.layernorm_bwd_fused(sv["x2"], f("norm1.weight"), dxn, B, H, W, add=dx1, windowed=True,
+                                                                                                     shift=shift, cast=dict(scale=next_scale, windowed=False))
+    else:
+        dx, g[prefix + "norm1.weight"], g[prefix + "norm1.bias"] = ops.layernorm_bwd_fused(sv["x2"], f("norm1.weight"), dxn, B, H, W, add=dx1, windowed=True, shift=shift)
+    side.join()
+    if next_scale is not _NO_CAST:
+        return dx.reshape(B, L, C), g, dyT_next
     return dx.reshape(B, L, C), g
 
 
@@ -579,10 +646,13 @@ class UformerTape:
                 # utils/model_utils.py:66-67) or head_dim-64 block (embed_dim 64) takes the op-by-op forward that keeps its intermediates and the
                 # op-level backward
                 # (a 4x4-window block -- the bottleneck of a model built for 64x64 patches -- keeps its intermediates in both forms)
-                fusable = self.recompute and C == 32 * cfg.num_heads[s] and wins[s] == 8
+                # (an Mlp block -- token_mlp 'ffn' -- has no block-level C backward and no native pack: it is packed through BlockPack and, in the
+                #  recompute form, reruns its op-by-op forward like a head_dim-64 block)
+                is_mlp = block_is_mlp(sd, prefix)
+                fusable = self.recompute and C == 32 * cfg.num_heads[s] and wins[s] == 8 and not is_mlp
                 # uf_pack_block_train (5 launches) covers C % 32 == 0; its pack also serves the op-by-op form as tensor views
-                native = C % 32 == 0 and C % cfg.num_heads[s] == 0 and _NATIVE_PACK and wins[s] == 8
-                if wins[s] == 4 and C % 32 == 0 and _NATIVE_PACK:
+                native = C % 32 == 0 and C % cfg.num_heads[s] == 0 and _NATIVE_PACK and wins[s] == 8 and not is_mlp
+                if wins[s] == 4 and C % 32 == 0 and _NATIVE_PACK and not is_mlp:
                     pk = self.packs[prefix] = native_block4_pack(sd, prefix, cfg.num_heads[s], T)
                 else:
                     pk = self.packs[prefix] = (NativeBlockPack(sd, prefix, cfg.num_heads[s], shifts[s][i], T) if native else
@@ -590,7 +660,7 @@ class UformerTape:
                 # a head_dim-64 block in the recompute form: the op-by-op forward, of which only the block's input is kept; its backward
                 # reruns the same unfused pieces (need_y=False: up to the stencil) and differentiates them -- the same kernels on the same
                 # operands as the kept form, so the same bits
-                unfused_rc = self.recompute and C == 64 * cfg.num_heads[s] and wins[s] == 8
+                unfused_rc = self.recompute and wins[s] == 8 and (C == 64 * cfg.num_heads[s] or (is_mlp and C == 32 * cfg.num_heads[s]))
                 if unfused_rc:
                     y, _ = lewin_block_forward(t.reshape(B, res[s][0] * res[s][1], C), sd, prefix, cfg.num_heads[s], shifts[s][i], T, dr, pk, hw=res[s])
                     self.saved_blocks[s].append(dict(x=t, drop=dr, pk=pk, unfused=(prefix, cfg.num_heads[s], shifts[s][i], res[s])))
