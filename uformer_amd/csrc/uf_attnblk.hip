@@ -248,8 +248,26 @@ struct NoWalk {   // f32 operands: phase 3 does not exist
 // of four, fetches the residual rows in the epilogue instead of ahead of the k-loop and adds the bias table one diagonal at a time.  Three independent
 // windows per CU = three waves per SIMD whose LayerNorm / softmax / GELU phases (VALU) and load / store bursts overlap each other's MFMAs.  Same MFMAs
 // on the same operands in the same order per accumulator: bit-identical to LR = 0.
-template <typename T, int C, int NT, int LR = 0, int TR = 0>
-__global__ __launch_bounds__(NT, LR == 3 ? 3 : (LR == 1 ? (C <= 32 ? 5 : (C == 64 ? 4 : 3)) : ((sizeof(T) == 2 && C <= 32) ? 4 : ((sizeof(T) == 2 && C == 64) ? 3 : 2)))) void attn_block_kernel(const AttnBlkParams p) {
+// NT = 64 / 128 (2-byte operand types at C <= 64): the WAVE-PER-WINDOW forms.  One wave (or two) owns a whole window: with one wave per
+// workgroup no other wave waits for it, so every barrier becomes a wait on the wave's own LDS traffic, the per-window fixed work (geometry, table
+// requests, row addresses, LN2 sums) is done once instead of once per wave, and a CU holds 7-13 independent windows instead of 3-5 whose loads,
+// VALU phases and stores interleave freely.  QTP (query tiles per unit, 0 = by head count as before) lets a wave that owns whole heads run
+// QT = 4, so that K and V are projected once per head (the units of one head differ only in their query tiles; at QT = 1 / 2 each of them
+// projects all 64 keys again).  Phase 0 keeps 8 lanes per row, LN2 its balanced trees over 16-channel tiles: same MFMAs on the same operands in
+// the same order per accumulator, same reduction trees -- bit-identical to every other form.
+// Second __launch_bounds__ argument = waves per SIMD.  256- and 512-thread workgroups put one (two) of their waves on each SIMD, so the number
+// is also workgroups per CU; a one-wave workgroup occupies one SIMD, so there it is windows per SIMD.
+template <typename T, int C, int NT, int LR> constexpr int attn_waves_per_simd() {
+    if (NT <= 128) return C <= 32 ? 3 : 2;      // <= 168 / 256 registers: LDS (12.2 / 21.8 KB per window) allows 13 / 7 windows per CU anyway
+    return LR == 3 ? 3 : (LR == 1 ? (C <= 32 ? 5 : (C == 64 ? 4 : 3)) : ((sizeof(T) == 2 && C <= 32) ? 4 : ((sizeof(T) == 2 && C == 64) ? 3 : 2)));
+}
+// the barrier between phases that exchange data through LDS: with one wave per workgroup only the wave's own LDS traffic has to land
+template <int WAVES> __device__ __forceinline__ void phase_barrier() {
+    if constexpr (WAVES == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    else lds_barrier();
+}
+template <typename T, int C, int NT, int LR = 0, int TR = 0, int QTP = 0>
+__global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void attn_block_kernel(const AttnBlkParams p) {
     constexpr bool ST = LR == 3;
     constexpr int SZ = sizeof(T);
     constexpr int WAVES = NT / 64;
@@ -257,7 +275,8 @@ __global__ __launch_bounds__(NT, LR == 3 ? 3 : (LR == 1 ? (C <= 32 ? 5 : (C == 6
     constexpr int SA = C * SZ + 16;                 // LDS row stride of Xn and O
     constexpr int KS = C / 32;                      // k-steps of the projections
     // unit = (head, group of QT query tiles); heads >= 4: one unit per head
-    constexpr int QT = HEADS >= 4 ? 4 : HEADS;      // query tiles per unit (4, 2 or 1)
+    constexpr int QT = QTP ? QTP : (HEADS >= 4 ? 4 : HEADS);      // query tiles per unit (4, 2 or 1)
+    static_assert(QT == 1 || QT == 2 || QT == 4, "query tiles per unit");
     constexpr int UNITS = HEADS * (4 / QT);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Xn = smem;
@@ -410,7 +429,7 @@ __global__ __launch_bounds__(NT, LR == 3 ? 3 : (LR == 1 ? (C <= 32 ? 5 : (C == 6
         else if (i < HEADS * 225 + 4 * C) Bq[i - HEADS * 225] = tabv[k];
     }
     stamp(1);
-    lds_barrier();
+    phase_barrier<WAVES>();
     stamp(2);
     // TR: an LDS operand tile [64][C] -> global rows, 16-byte pieces, consecutive threads on consecutive pieces of a row
     auto tile_out = [&](const char* tile, void* dst, bool token_order) {
@@ -745,7 +764,7 @@ __global__ __launch_bounds__(NT, LR == 3 ? 3 : (LR == 1 ? (C <= 32 ? 5 : (C == 6
     if constexpr (ST) {
 #pragma unroll
         for (int ui = 0; ui < UPW; ++ui) unit(wave + ui * WAVES, ui);
-        lds_barrier();                                            // every wave has made its last read of Xn
+        phase_barrier<WAVES>();                                            // every wave has made its last read of Xn
 #pragma unroll
         for (int ui = 0; ui < UPW; ++ui) {
             const int u = wave + ui * WAVES, h = u / (4 / QT), q0 = (u % (4 / QT)) * QT;
@@ -810,7 +829,7 @@ __global__ __launch_bounds__(NT, LR == 3 ? 3 : (LR == 1 ? (C <= 32 ? 5 : (C == 6
             }
         };
         if constexpr (HOIST) proj_requests();      // in flight across the barrier (UF_HOIST): waves that finish phase 1 early wait there anyway
-        lds_barrier();
+        phase_barrier<WAVES>();
         stamp(6);
         if constexpr (TR) tile_out(Os, p.s_o, false);
         if constexpr (!HOIST) proj_requests();
@@ -872,9 +891,13 @@ __global__ __launch_bounds__(NT, LR == 3 ? 3 : (LR == 1 ? (C <= 32 ? 5 : (C == 6
                             part[i] = red_xor32<RedSum>(red_xor16<RedSum>(part[i]));   // the tile's 16 channels
                         }
                         const float sacc = tree_sum<TNW>(part);
-                        if (fg == 0) Red[(pass * WAVES + wave) * 64 + (wm * TMW + j) * 16 + fr] = sacc;
+                        if constexpr (WN == 1) {      // the wave holds whole rows: the tree ends here (every lane has the row's sum), no exchange
+                            if (pass == 0) mean[j] = sacc * (1.0f / C);
+                            else rstd[j] = 1.0f / sqrtf(sacc * (1.0f / C) + 1e-5f);
+                        } else if (fg == 0) Red[(pass * WAVES + wave) * 64 + (wm * TMW + j) * 16 + fr] = sacc;
                     }
-                    lds_barrier();
+                    if constexpr (WN > 1) {
+                    phase_barrier<WAVES>();
 #pragma unroll
                     for (int j = 0; j < TMW; ++j) {
                         float wsum[WN];
@@ -883,6 +906,7 @@ __global__ __launch_bounds__(NT, LR == 3 ? 3 : (LR == 1 ? (C <= 32 ? 5 : (C == 6
                         const float tot = tree_sum<WN>(wsum);
                         if (pass == 0) mean[j] = tot * (1.0f / C);
                         else rstd[j] = 1.0f / sqrtf(tot * (1.0f / C) + 1e-5f);
+                    }
                     }
                 }
 #pragma unroll
@@ -898,7 +922,7 @@ __global__ __launch_bounds__(NT, LR == 3 ? 3 : (LR == 1 ? (C <= 32 ? 5 : (C == 6
     }
     if constexpr (SZ == 2) {
         if (p.h1) {
-            lds_barrier();
+            phase_barrier<WAVES>();
             stamp(11);
             if constexpr (TR) tile_out(Xn, p.s_z, true);
             if constexpr (!HOIST) fc1w.first(reinterpret_cast<const T*>(p.W1), wave, lane);
@@ -909,11 +933,11 @@ __global__ __launch_bounds__(NT, LR == 3 ? 3 : (LR == 1 ? (C <= 32 ? 5 : (C == 6
     census.end(p.tbuf, bw);
 }
 
-template <typename T, int C, int NT, int LR = 0, int TR = 0>
+template <typename T, int C, int NT, int LR = 0, int TR = 0, int QTP = 0>
 int launch_one(const AttnBlkParams& p, hipStream_t st) {
     constexpr int smem = (LR == 3 ? 1 : 2) * 64 * (C * (int)sizeof(T) + 16) + (C / 32) * 225 * 4 + 2 * (NT / 64) * 64 * 4 + 4 * C * 4;
     static_assert(smem <= 160 * 1024, "LDS budget");
-    auto kern = attn_block_kernel<T, C, NT, LR, TR>;
+    auto kern = attn_block_kernel<T, C, NT, LR, TR, QTP>;
     static bool lds_done[64] = {};
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, lds_done, "attn_block")) return rc;
     char name[96] = "";
@@ -962,20 +986,34 @@ int launch_attn_block(const uf_block_params* bp, float* x, int ld, int B, int H,
     p.tbuf = debug_get_tbuf();
 
     // Form by shape; UF_VARIANT="attn=k" forces one (A/B runs, bit-identity test): 0 the first form, 1 the low-register form at C <= 128 with the tighter
-    // register bound (one more workgroup per CU), 2 the same code at the occupancy of the first form, 3 the single-operand-tile form at C = 256.
+    // register bound (one more workgroup per CU), 2 the same code at the occupancy of the first form, 3 the single-operand-tile form at C = 256,
+    // 4 / 5 the wave-per-window forms (one / two waves per window) at C <= 64 with 2-byte operands; wherever a forced form is not built the shape picks.
     // Defaults from the same-box A/B of the bit-identical forms (profiles/r04_run4.txt, ms per step: first / 1 / 2):
     // C = 32 (enc0) 0.187 / 0.212 / 0.172 -> 2; C = 128 with >= 4096 windows (dec2) 0.409 / 0.383 / 0.406 -> 1; everything else stays
     // on the first form (C = 128 with 1024 windows 0.445 / 0.445 / 0.467, C = 64 0.361 / 0.373 / 0.366 and 0.177 / 0.179 / 0.183).
     // The single-tile form (3) is NOT a default: bit-identical, three workgroups per CU, 128 vs 136 us on the isolated dec1 launch but 123 vs 117 us
     // inside the model and the MFMA pipe busy 26.5 % instead of 27.7 % (profiles/r06_run3_stages.txt, r06_run4_ab.txt, r06_pmc?_st?_attn_leff.csv).
+    // Wave-per-window forms (profiles/attn_wave.json; us per launch with fc1, five interleaved rounds, first form / 4 / 5):
+    // C = 32 with 16384 windows 169-175 (form 2, the default until then: 167.5 in the model) / 124-127 / 140-145, with 8192 windows 80-85 / 61-64 / 61-65 -> 4 from 8192
+    // windows up.  (4 also won every round at 1024-4096 windows with fc1, 27-28 / 22-23 at 1024, but without fc1 it is 8.3 against 8.0 there: not switched.)
+    // C = 64 is NOT switched: 4 wins every round at 16384 windows (333-374 / 301-311 / 325-329) and at 8192 (158-163 / 152-162 / 152-161), but
+    // loses at 4096 (74-79 / 84-90 / 73-76), 2048 (41-43 / 54-57 / 43-44) and below; 5 wins only at 1024 windows (29-30 / 33-35 / 24-25).  The
+    // C = 64 launches of the two-stream forward have 8192 and 2048 windows: a gain inside the run-to-run spread of the step, left for a later A/B.
     const int forced = variant("attn", -1);
     const int lr = (forced >= 0 && forced <= 2) ? forced : (forced == 3 ? 0 : (C == 32 ? 2 : ((C == 128 && p.n_windows >= 4096) ? 1 : 0)));
     const bool st256 = forced == 3;
+    const int nt_small = forced == 4 ? 64 : (forced == 5 ? 128 : ((forced < 0 && C == 32 && p.n_windows >= 8192) ? 64 : 0));   // wave-per-window forms
 #define UF_AB(TT, CV, NTV) return launch_one<TT, CV, NTV>(p, st)
 #define UF_AB_HALF(TT)                                                                                                              \
         switch (C) {                                                                                                                    \
-            case 32: if (lr == 1) return launch_one<TT, 32, 256, 1>(p, st); if (lr == 2) return launch_one<TT, 32, 256, 2>(p, st); UF_AB(TT, 32, 256);      \
-            case 64: if (lr == 1) return launch_one<TT, 64, 256, 1>(p, st); if (lr == 2) return launch_one<TT, 64, 256, 2>(p, st); UF_AB(TT, 64, 256);      \
+            case 32:                                                                                                                    \
+                if (nt_small == 64) return launch_one<TT, 32, 64, 0, 0, 4>(p, st);    /* one wave: its head with all four query tiles */      \
+                if (nt_small == 128) return launch_one<TT, 32, 128, 0, 0, 2>(p, st);  /* two waves: two query tiles each */                   \
+                if (lr == 1) return launch_one<TT, 32, 256, 1>(p, st); if (lr == 2) return launch_one<TT, 32, 256, 2>(p, st); UF_AB(TT, 32, 256);      \
+            case 64:                                                                                                                    \
+                if (nt_small == 64) return launch_one<TT, 64, 64, 0, 0, 4>(p, st);    /* one wave: both heads, one after the other */         \
+                if (nt_small == 128) return launch_one<TT, 64, 128, 0, 0, 4>(p, st);  /* two waves: one head each */                          \
+                if (lr == 1) return launch_one<TT, 64, 256, 1>(p, st); if (lr == 2) return launch_one<TT, 64, 256, 2>(p, st); UF_AB(TT, 64, 256);      \
             case 128: if (lr == 1) return launch_one<TT, 128, 256, 1>(p, st); if (lr == 2) return launch_one<TT, 128, 256, 2>(p, st); UF_AB(TT, 128, 256);                                                                                              \
             case 256:                                                                                                                   \
                 if (p.n_windows <= 256) UF_AB(TT, 256, 512);   /* one workgroup per CU at most: 8 waves (one head each) instead of 4 */ \

@@ -17,6 +17,7 @@ static thread_local char g_err[512] = "";
 // UF_VARIANT="key=value,key=value,...": the ONE environment variable that selects between launch variants of a kernel for A/B runs and for the
 // bit-identity tests (round 6: it replaces eight separate UF_* switches).  Every variant of a key computes identical bits; without the key the shape picks.
 //   attn=0|1|2|3    attn_block: first form / low-register form with tight / relaxed register bounds / single-operand-tile form (C = 256)
+//   attn=4|5        attn_block at C <= 64, 2-byte operands: one wave / two waves per window instead of four (other widths: the shape picks)
 //   leff2=1|2       leff2: 8 producer waves wherever they are built / never
 //   persist=0|1     leff2: one tile per workgroup / the persistent tile walk everywhere
 //   gemm_dma=0|1    gemm_kernel: register-staged / LDS-DMA operand staging on every shape that supports it
