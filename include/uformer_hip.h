@@ -107,6 +107,22 @@ int uf_ln_qkv_fwd(const float* x, int ld, const float* gamma, const float* beta,
                   const float* modulator /* (64,C) or NULL */, const void* Wqkv_fm, const float* bqkv,
                   void* q, void* k, void* vt, int B, int H, int W, int C, int heads, int shift,
                   uf_dtype dtype, void* stream);
+/* ---- the same producer for a ConvProjection (token_projection 'conv', model.py:381-410): LN1 -> roll -> window_partition -> +modulator, then
+ * per 8x8 window and for each of j = q, k, v a SepConv2d (model.py:344-371) on the window's [64][C] tile xw, row t = 8 y + x:
+ *   P_j[t][c] = ReLU( bdw_j[c] + sum_{ky,kx} dw_j[c][ky][kx] * xw[(y+ky-1) 8 + (x+kx-1)][c] )    terms outside the 8x8 WINDOW are zero (cross-correlation, as nn.Conv2d)
+ *   out_j     = P_j Wpw_j^T + bpw_j
+ * with the outputs in the layouts of uf_qkv_fwd (q times hd^-0.5, k, v^T), so uf_window_attention_fwd consumes them unchanged.
+ * Rounding points: xw is rounded to T in LDS (as uf_ln_qkv_fwd's operand tile); the stencil, the bias and the ReLU run in f32 and P_j is rounded to T
+ * as a stored activation is; the MFMA accumulates in f32, then the f32 bias is added, then (q) the scale, and the result is rounded to T.
+ * One workgroup per window: LDS holds the xw tile and one P tile, and the three thirds run one after the other.  f32 at C = 512 does not fit two tiles:
+ * there xw is first written by the windowed LayerNorm kernel into the window's own 64 C elements of vt (which that window overwrites last) and the
+ * stencil reads it from there.  C in {16,32,64,128,256,512}, hd = C / heads in {16,32,64}; x, the weights and the outputs 16-byte aligned, ld % 4 == 0. */
+int uf_ln_convqkv_fwd(const float* x, int ld, const float* gamma, const float* beta, const float* modulator /* (64,C) or NULL */,
+                      const float* dw9 /* f32 (3,9,C): to_q | to_k | to_v depthwise, tap-major (tap = ky * 3 + kx) */,
+                      const float* bdw /* f32 (3,C) */,
+                      const void* Wpw_fm /* T (3C,C) fragment-major: cat(to_q, to_k, to_v).pointwise.weight */,
+                      const float* bpw /* f32 (3C) */,
+                      void* q, void* k, void* vt, int B, int H, int W, int C, int heads, int shift, uf_dtype dtype, void* stream);
 /* ---- a5+a10 fused: LN2 -> linear1 -> GELU (model.py:987, :657-658).  x f32 [M] rows (stride ld),
  * W1_fm = fragment-major T[N][C], b1 f32[N], out T[M][N]. */
 int uf_ln_linear_gelu_fwd(const float* x, int ld, const float* gamma, const float* beta,
@@ -178,6 +194,12 @@ typedef struct uf_block_params {
     const float* b2;        /* (C) */
     int32_t shift;          /* 0 or 4, decided at construction (model.py:1030, :863-866) */
     int32_t heads;
+    /* ConvProjection (token_projection 'conv', model.py:381-410); both NULL: a LinearProjection block.  Both set: wqkv_fm / bqkv hold the three
+       POINTWISE weights cat(to_q, to_k, to_v).pointwise.weight (3C,C) fragment-major and their biases, the attention half runs as three launches
+       with uf_ln_convqkv_fwd as the producer (every width up to 512, head_dim and dtype, with or without a caller mask), and the training entry
+       points, 4x4-window blocks and C = 1024 return UF_ERR_UNSUPPORTED */
+    const float* qkv_dw9;   /* (3,9,C) tap-major repacks of attn.qkv.to_{q,k,v}.depthwise.weight (C,1,3,3) */
+    const float* qkv_bdw;   /* (3,C) attn.qkv.to_{q,k,v}.depthwise.bias */
 } uf_block_params;
 
 /* bytes of scratch a block needs for M = B*H*W tokens of width C */

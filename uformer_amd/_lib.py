@@ -23,7 +23,7 @@ class BlockParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "norm1_w", "norm1_b", "modulator", "rpb_dense", "rpb_fm", "rpb_tab", "wqkv_fm", "bqkv", "wproj", "wproj_fm", "bproj",
         "norm2_w", "norm2_b", "w1_fm", "b1", "wdw9", "bdw", "w2_fm", "b2")] + [
-        ("shift", C.c_int32), ("heads", C.c_int32)]
+        ("shift", C.c_int32), ("heads", C.c_int32), ("qkv_dw9", C.c_void_p), ("qkv_bdw", C.c_void_p)]
 
 
 class BlockTrainParams(C.Structure):
@@ -96,6 +96,7 @@ SIGNATURES = {
     "uf_linear_fwd": (I, [P, P, P, P, I, I, I, I, I, P]),
     "uf_qkv_fwd": (I, [P, P, P, P, P, P, I, I, I, I, P]),
     "uf_ln_qkv_fwd": (I, [P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "uf_ln_convqkv_fwd": (I, [P, I, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
     "uf_ln_linear_gelu_fwd": (I, [P, I, P, P, P, P, P, I, I, I, I, P]),
     "uf_window_attention_fwd": (I, [P, P, P, P, P, I, P, I, I, I, I, I, I, I, P]),
     "uf_dwconv3x3_gelu_fwd": (I, [P, P, P, P, I, I, I, I, I, P]),

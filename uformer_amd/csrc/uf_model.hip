@@ -53,8 +53,14 @@ int carve(BlockWs& w, void* ws, size_t ws_bytes, size_t M, size_t C, uf_dtype dt
 // wdw9 = bdw = NULL, and w1_fm / b1 / w2_fm / b2 are fc1 / fc2.
 bool mlp_block(const uf_block_params* p) { return !p->wdw9 && !p->bdw; }
 
+// A block built with token_projection = 'conv' (reference ConvProjection, model.py:381-410) carries the depthwise taps and biases of to_q | to_k | to_v
+// in qkv_dw9 / qkv_bdw; wqkv_fm / bqkv are then the three pointwise convolutions.  Inference only, on the three-launch attention route.
+bool conv_block(const uf_block_params* p) { return p->qkv_dw9 && p->qkv_bdw; }
+
 int check_block_args(const uf_block_params* p, const float* x, int ld, int B, int H, int W, int C, uf_dtype dtype) {
     UF_REQUIRE(p && x, UF_ERR_NULL, "block: null pointer");
+    UF_REQUIRE(!p->qkv_dw9 == !p->qkv_bdw, UF_ERR_NULL, "block: qkv_dw9 and qkv_bdw must both be set (ConvProjection, token_projection = 'conv') or both be NULL");
+    UF_REQUIRE(!(conv_block(p) && wide_block((size_t)C)), UF_ERR_UNSUPPORTED, "block: token_projection = 'conv' is built for C <= 512 (got C=%d)", C);
     UF_REQUIRE(!p->wdw9 == !p->bdw, UF_ERR_NULL, "block: wdw9 and bdw must both be set (LeFF) or both be NULL (Mlp, token_mlp = 'ffn')");
     UF_REQUIRE(!(mlp_block(p) && wide_block((size_t)C)), UF_ERR_UNSUPPORTED, "block: token_mlp = 'ffn' is built for C <= 512 (got C=%d)", C);
     UF_REQUIRE(dtype_ok(dtype), UF_ERR_UNSUPPORTED, "block: dtype %d", (int)dtype);
@@ -79,7 +85,7 @@ int attn_half(const uf_block_params* p, float* x, int ld, int B, int H, int W, i
     // window_reverse and the residual never leave the CU                       (model.py:951-986)
     // (Stages with fewer windows than CUs -- 4 ... 64 at small batches -- stay on the fused kernel too: the 3-kernel path, whose GEMMs tile over the
     // whole chip, measured slower at every batch size from 1 to 16: profiles/r03_unfuse.txt, profiles/r05_run5_unfuse.txt.)
-    if (attn_block_supported(p, user_mask, dtype, C, heads)) {
+    if (!conv_block(p) && attn_block_supported(p, user_mask, dtype, C, heads)) {
         const bool with_fc1 = fc1_done && dtype_half(dtype) && C >= 32 && !mlp_block(p);   // an Mlp block: no phase 3, uf_ffn_fwd follows
         if (fc1_done) *fc1_done = with_fc1;
         return launch_attn_block(p, x, ld, B, H, W, C, dtype, with_fc1 ? w.h1 : nullptr, st, drop);
@@ -91,7 +97,10 @@ int attn_half(const uf_block_params* p, float* x, int ld, int B, int H, int W, i
     char* k = q + (size_t)M * C * sz;
     char* vt = k + (size_t)M * C * sz;
     int rc;
-    if (wide_block(C)) {
+    if (conv_block(p)) {   // the same producer with the three window stencils in front of the GEMM (model.py:381-410)
+        rc = uf_ln_convqkv_fwd(x, ld, p->norm1_w, p->norm1_b, p->modulator, p->qkv_dw9, p->qkv_bdw, p->wqkv_fm, p->bqkv, q, k, vt, B, H, W, C, heads,
+                               p->shift, dtype, st);
+    } else if (wide_block(C)) {
         rc = launch_layernorm(x, ld, p->norm1_w, p->norm1_b, p->modulator, w.a, M, H, W, C, 1, p->shift, dtype, st);
         if (rc) return rc;
         rc = launch_unpack_weight_fm(p->wqkv_fm, w.wr, 3 * C, C, dtype, st);
@@ -236,6 +245,7 @@ extern "C" int uf_lewin_attn_train_fwd(const uf_block_params* p, const float* x,
                                        void* stream) {
     int rc = check_block_args(p, x, ld, B, H, W, C, dtype);
     if (rc) return rc;
+    UF_REQUIRE(!conv_block(p), UF_ERR_UNSUPPORTED, "uf_lewin_attn_train_fwd: token_projection = 'conv' runs inference only");
     UF_REQUIRE(x1 && xn && q && k && vt && o && z && a1, UF_ERR_NULL, "uf_lewin_attn_train_fwd: null output pointer");
     UF_REQUIRE(x1 != x && ld1 >= C && ld1 % 4 == 0, UF_ERR_SHAPE, "uf_lewin_attn_train_fwd: x1 must be out of place, ld1=%d", ld1);
     UF_REQUIRE(dtype_half(dtype) && attn_block_supported(p, nullptr, dtype, C, p->heads), UF_ERR_UNSUPPORTED,
@@ -249,6 +259,7 @@ extern "C" int uf_lewin_block_train_fwd(const uf_block_params* p, float* x, int 
                                         const float* drop_leff, uf_dtype dtype, void* ws, size_t ws_bytes, void* stream) {
     int rc = check_block_args(p, x, ld, B, H, W, C, dtype);
     if (rc) return rc;
+    UF_REQUIRE(!conv_block(p), UF_ERR_UNSUPPORTED, "uf_lewin_block_train_fwd: token_projection = 'conv' runs inference only");
     BlockWs w;
     rc = carve(w, ws, ws_bytes, (size_t)B * H * W, C, dtype);
     if (rc) return rc;

@@ -71,14 +71,67 @@ class LinearProjection(nn.Module):
         return q_L * self.dim * self.inner_dim + kv_L * self.dim * self.inner_dim * 2
 
 
+CONV_PROJECTION_WIDTHS = (16, 32, 64, 128, 256, 512)     # uf_ln_convqkv_fwd
+
+
+class SepConv2d(nn.Module):
+    """model.py:344-378: depthwise conv -> ReLU -> pointwise 1x1 conv.  Holds the parameters; inside a block the three of a ConvProjection
+    run in one ``uf_ln_convqkv_fwd`` launch."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, act_layer=nn.ReLU):
+        super().__init__()
+        if kernel_size != 3 or stride != 1 or padding != 1 or dilation != 1 or act_layer is not nn.ReLU:
+            raise NotImplementedError("SepConv2d: only the configuration ConvProjection builds (3x3, stride 1, padding 1, ReLU; model.py:389-392)")
+        self.depthwise = nn.Conv2d(in_channels, in_channels, kernel_size=kernel_size, stride=stride, padding=padding, dilation=dilation,
+                                   groups=in_channels)
+        self.pointwise = nn.Conv2d(in_channels, out_channels, kernel_size=1)
+        self.act_layer = act_layer()
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.kernel_size = kernel_size
+        self.stride = stride
+
+    def flops(self, HW):
+        return HW * self.in_channels * self.kernel_size ** 2 / self.stride ** 2 + HW * self.in_channels * self.out_channels
+
+
+class ConvProjection(nn.Module):
+    """model.py:381-418 (``token_projection='conv'``): ``to_q``, ``to_k``, ``to_v``, each a SepConv2d over the 8x8 image of one window."""
+
+    def __init__(self, dim, heads=8, dim_head=64, kernel_size=3, q_stride=1, k_stride=1, v_stride=1, dropout=0., last_stage=False, bias=True):
+        super().__init__()
+        if kernel_size != 3 or (q_stride, k_stride, v_stride) != (1, 1, 1) or not bias:
+            raise NotImplementedError("ConvProjection: 3x3 kernels, stride 1 and biases only (WindowAttention's configuration, model.py:481)")
+        inner_dim = dim_head * heads
+        if inner_dim != dim:
+            raise NotImplementedError("ConvProjection: heads * dim_head must equal dim (model.py:481)")
+        self.heads = heads
+        pad = (kernel_size - q_stride) // 2
+        self.to_q = SepConv2d(dim, inner_dim, kernel_size, q_stride, pad)
+        self.to_k = SepConv2d(dim, inner_dim, kernel_size, k_stride, pad)
+        self.to_v = SepConv2d(dim, inner_dim, kernel_size, v_stride, pad)
+        self.dim = dim
+        self.inner_dim = inner_dim
+
+    def flops(self, q_L, kv_L=None):
+        kv_L = kv_L or q_L
+        return self.to_q.flops(q_L) + self.to_k.flops(kv_L) + self.to_v.flops(kv_L)
+
+
 class WindowAttention(nn.Module):
-    """model.py:452-546 with ``token_projection='linear'`` (the only one any arch selects)."""
+    """model.py:452-546; ``token_projection`` 'linear' (every get_arch architecture) or 'conv' (ConvProjection; 8x8 windows, inference inside a
+    LeWinTransformerBlock, where it runs fused behind norm1: uf_ln_convqkv_fwd)."""
 
     def __init__(self, dim, win_size, num_heads, token_projection='linear', qkv_bias=True, qk_scale=None,
                  attn_drop=0., proj_drop=0.):
         super().__init__()
-        if token_projection != 'linear':
-            raise NotImplementedError("only token_projection='linear' is on the hot path (utils/model_utils.py:65-78)")
+        if token_projection not in ('linear', 'conv'):
+            raise NotImplementedError(f"token_projection={token_projection!r}: 'linear' and 'conv' are built (model.py:480-485)")
+        if token_projection == 'conv' and (tuple(win_size) != (8, 8) or dim not in CONV_PROJECTION_WIDTHS or dim % num_heads
+                                           or dim // num_heads not in (16, 32, 64)):
+            raise NotImplementedError(f"token_projection='conv' is built for 8x8-window blocks of width 16 ... 512 with head_dim 16, 32 or 64 "
+                                      f"(uf_ln_convqkv_fwd); this block has width {dim}, {num_heads} heads and window {tuple(win_size)} (img_size 64 "
+                                      f"and embed_dim 64 take token_projection='linear' only)")
         if qk_scale is not None or attn_drop or proj_drop:
             raise NotImplementedError("qk_scale / attention dropout are never set by the reference archs")
         self.dim = dim
@@ -90,7 +143,10 @@ class WindowAttention(nn.Module):
             torch.zeros((2 * self.win_size[0] - 1) * (2 * self.win_size[1] - 1), num_heads))
         self.register_buffer("relative_position_index", relative_position_index(self.win_size[0]))
         nn.init.trunc_normal_(self.relative_position_bias_table, std=.02)
-        self.qkv = LinearProjection(dim, num_heads, dim // num_heads, bias=qkv_bias)
+        if token_projection == 'conv':
+            self.qkv = ConvProjection(dim, num_heads, dim // num_heads, bias=qkv_bias)
+        else:
+            self.qkv = LinearProjection(dim, num_heads, dim // num_heads, bias=qkv_bias)
         self.token_projection = token_projection
         self.proj = nn.Linear(dim, dim)
 
@@ -99,6 +155,9 @@ class WindowAttention(nn.Module):
         """x: (B_, 64, C) window tokens (B_, 16, C at win_size 4).  ``mask`` (nW,64,64) additive, as in model.py:508-512."""
         if attn_kv is not None:
             raise NotImplementedError("attn_kv (cross-modulator) is out of scope: never enabled by get_arch")
+        if self.token_projection == 'conv':
+            raise NotImplementedError("token_projection='conv': the ConvProjection runs fused behind norm1 (uf_ln_convqkv_fwd); call the "
+                                      "LeWinTransformerBlock, there is no stand-alone WindowAttention forward for it")
         B_, N, Cc = x.shape
         if self.win_size == (4, 4):
             if mask is not None or shift:
@@ -133,7 +192,7 @@ class WindowAttention(nn.Module):
     def flops(self, H, W):
         N = self.win_size[0] * self.win_size[1]
         nW = H * W / N
-        flops = self.qkv.flops(H * W, H * W)
+        flops = self.qkv.flops(H * W, H * W)     # ConvProjection: + 27 depthwise taps per token and channel (model.py:373-377, :412-418)
         flops += nW * self.num_heads * N * (self.dim // self.num_heads) * N * 2
         flops += nW * N * self.dim * self.dim
         return flops
@@ -280,7 +339,8 @@ class OutputProj(nn.Module):
 
 
 class LeWinTransformerBlock(nn.Module):
-    """model.py:850-1008 (``token_mlp`` 'leff', or 'ffn' / 'mlp' for the reference's Mlp; no cross-modulator)."""
+    """model.py:850-1008 (``token_mlp`` 'leff', or 'ffn' / 'mlp' for the reference's Mlp; ``token_projection`` 'linear', or 'conv' for the
+    reference's ConvProjection, inference only; no cross-modulator)."""
 
     def __init__(self, dim, input_resolution, num_heads, win_size=8, shift_size=0, mlp_ratio=4., qkv_bias=True,
                  qk_scale=None, drop=0., attn_drop=0., drop_path=0., act_layer=nn.GELU, norm_layer=nn.LayerNorm,
@@ -300,6 +360,7 @@ class LeWinTransformerBlock(nn.Module):
         self.shift_size = shift_size
         self.mlp_ratio = mlp_ratio
         self.token_mlp = token_mlp
+        self.token_projection = token_projection
         if min(self.input_resolution) <= self.win_size:   # model.py:863-866
             self.shift_size = 0
             self.win_size = min(self.input_resolution)
@@ -357,6 +418,8 @@ class LeWinTransformerBlock(nn.Module):
         Otherwise: the fused inference kernels (DropPath is the identity)."""
         if torch.is_grad_enabled() and mask is None and (self.training or x.requires_grad or any(p.requires_grad for p in self.parameters())):
             from . import train
+            if self.token_projection == 'conv':
+                raise NotImplementedError(train.TOKEN_PROJECTION_TRAINING)
             if not x.is_cuda:
                 raise UformerHipError("LeWinTransformerBlock runs on the GPU only; there is no CPU path")
             named = [(n, t) for n, t in self.state_dict(keep_vars=True).items()]
@@ -406,6 +469,9 @@ class BasicUformerLayer(nn.Module):
                  qk_scale=None, drop=0., attn_drop=0., drop_path=0., norm_layer=nn.LayerNorm, use_checkpoint=False,
                  token_projection='linear', token_mlp='ffn', shift_flag=True, modulator=False, cross_modulator=False):
         super().__init__()
+        if use_checkpoint and token_projection == 'conv':
+            from .train import TOKEN_PROJECTION_TRAINING
+            raise NotImplementedError("use_checkpoint: " + TOKEN_PROJECTION_TRAINING)
         self.dim = dim
         self.input_resolution = input_resolution
         self.depth = depth
@@ -453,7 +519,7 @@ class Uformer(nn.Module):
         self.compute_dtype = compute_dtype
         self.cfg = UformerConfig(img_size=img_size, in_chans=in_chans, dd_in=dd_in, embed_dim=embed_dim,
                                  depths=tuple(depths), num_heads=tuple(num_heads), win_size=win_size, mlp_ratio=mlp_ratio,
-                                 modulator=modulator, shift_flag=shift_flag, token_mlp=token_mlp)
+                                 modulator=modulator, shift_flag=shift_flag, token_mlp=token_mlp, token_projection=token_projection)
         bad = self.cfg.unsupported_clamp() if win_size == 8 else None
         if bad is not None:       # model.py:863-866 clamps a stage's window to its resolution; built: 8, and 4 for the bottleneck alone
             s_, res_, win_ = bad
@@ -588,6 +654,9 @@ class Uformer(nn.Module):
 
     # ---- forward -----------------------------------------------------------------------------
     def forward(self, x: Tensor, mask: Optional[Tensor] = None) -> Tensor:
+        if self.token_projection == 'conv' and torch.is_grad_enabled() and (self.training or x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            from .train import TOKEN_PROJECTION_TRAINING
+            raise NotImplementedError(TOKEN_PROJECTION_TRAINING)
         if self.cfg.stage_windows()[4] == 4 and x.dim() == 4:     # built for 64x64 patches: 4 downsamplings x the bottleneck's window 4
             for name, n in (("H", x.shape[2]), ("W", x.shape[3])):
                 if n % 64 or n <= 0:
@@ -701,7 +770,9 @@ class Uformer(nn.Module):
         for s in range(9):
             L = (r // div[s]) ** 2
             # LeFF: the depthwise conv's 9 taps over 4C channels (36); Mlp has none (model.py:644-651)
-            total += self.cfg.depths[s] * L * dims[s] * (12 * dims[s] + 2 * wins[s] ** 2 + (0 if self.cfg.mlp_is_ffn() else 36))
+            # ConvProjection: three depthwise 3x3 convolutions in front of the q | k | v GEMM (27 taps per channel, model.py:373-377)
+            total += self.cfg.depths[s] * L * dims[s] * (12 * dims[s] + 2 * wins[s] ** 2 + (0 if self.cfg.mlp_is_ffn() else 36)
+                                                         + (27 if self.cfg.token_projection == 'conv' else 0))
         for s in range(4):
             L = (r // div[s]) ** 2
             total += (L // 4) * dims[s] * 2 * dims[s] * 16
@@ -851,9 +922,11 @@ class UNet(nn.Module):
         return flops
 
 
-def get_arch(arch: str, train_ps: int = 128, dd_in: int = 3, embed_dim: int = 32, compute_dtype=torch.bfloat16) -> nn.Module:
-    """utils/model_utils.py:56-81 ``get_arch(opt)`` with the option fields as arguments."""
-    common = dict(win_size=8, token_projection='linear', token_mlp='leff', modulator=True, compute_dtype=compute_dtype)
+def get_arch(arch: str, train_ps: int = 128, dd_in: int = 3, embed_dim: int = 32, compute_dtype=torch.bfloat16,
+             token_projection: str = 'linear') -> nn.Module:
+    """utils/model_utils.py:56-81 ``get_arch(opt)`` with the option fields as arguments (``token_projection``: its hard-coded 'linear', or
+    'conv' for the paper's ablation row)."""
+    common = dict(win_size=8, token_projection=token_projection, token_mlp='leff', modulator=True, compute_dtype=compute_dtype)
     if arch == 'Uformer':
         return Uformer(img_size=train_ps, embed_dim=embed_dim, **common)
     if arch == 'Uformer_T':

@@ -273,6 +273,32 @@ def ln_qkv(x: Tensor, gamma: Tensor, beta: Tensor, wqkv: Tensor, bqkv: Tensor, h
     return q, k, vt
 
 
+def ln_conv_qkv(x: Tensor, gamma: Tensor, beta: Tensor, dw9: Tensor, bdw: Tensor, wpw: Tensor, bpw: Tensor, heads: int, *, B: int, H: int, W: int,
+                shift: int = 0, modulator: Optional[Tensor] = None, C: Optional[int] = None):
+    """Fused LN1 -> roll -> partition -> +modulator -> ConvProjection (model.py:952-969, :381-410): per 8x8 window and for each of q, k, v a
+    depthwise 3x3 (zero padding at the WINDOW border) + bias + ReLU, then the pointwise 1x1 + bias; q (scaled), k, v^T as ``ln_qkv``
+    (uf_ln_convqkv_fwd).  x f32 (B*H*W, ld) contiguous with the channels in columns [0, C) (``C`` default: ld); dw9 f32 (3, 9, C) tap-major and
+    bdw f32 (3, C) for q | k | v (packing.pack_conv_projection); wpw T (3C, C) row-major (packed fragment-major here); bpw f32 (3C,)."""
+    _dev(x, gamma, beta, dw9, bdw, wpw, bpw, modulator)
+    dt = uf_dtype(wpw.dtype)
+    x = _c(x, torch.float32)
+    M, ld = x.shape
+    Cc = ld if C is None else int(C)
+    if tuple(wpw.shape) != (3 * Cc, Cc) or tuple(dw9.shape) != (3, 9, Cc) or tuple(bdw.shape) != (3, Cc) or bpw.numel() != 3 * Cc:
+        raise UformerHipError(f"ln_conv_qkv: dw9 {tuple(dw9.shape)} / bdw {tuple(bdw.shape)} / wpw {tuple(wpw.shape)} / bpw {tuple(bpw.shape)} "
+                              f"do not match C = {Cc}")
+    hd = Cc // heads
+    q = torch.empty((M // 64, heads, 64, hd), dtype=wpw.dtype, device=x.device)
+    k = torch.empty_like(q)
+    vt = torch.empty((M // 64, heads, hd, 64), dtype=wpw.dtype, device=x.device)
+    keep = (_c(gamma, torch.float32), _c(beta, torch.float32), None if modulator is None else _c(modulator, torch.float32), _c(dw9, torch.float32),
+            _c(bdw, torch.float32), _pack_frag(wpw), _c(bpw, torch.float32))
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().uf_ln_convqkv_fwd(_ptr(x), ld, *[_ptr(t) for t in keep], _ptr(q), _ptr(k), _ptr(vt), B, H, W, Cc, heads, shift, dt,
+                                                 _stream()), "uf_ln_convqkv_fwd")
+    return q, k, vt
+
+
 def ln_linear_gelu(x: Tensor, gamma: Tensor, beta: Tensor, w1: Tensor, b1: Tensor) -> Tensor:
     """Fused LN2 -> linear1 -> GELU (model.py:987, :657-658).  x f32 (M, C); w1 T (N, C) -> T (M, N)."""
     _dev(x, gamma, beta, w1, b1)

@@ -73,6 +73,23 @@ def pack_dwconv(w: Tensor) -> Tensor:
     return w.detach().reshape(w.shape[0], 9).t().contiguous().float()
 
 
+def conv_projection_keys(sd: Dict[str, Tensor], prefix: str) -> bool:
+    """True where the block under ``prefix`` carries a ConvProjection (``token_projection='conv'``, model.py:381-392)."""
+    return (prefix + "attn.qkv.to_q.depthwise.weight") in sd
+
+
+def pack_conv_projection(sd: Dict[str, Tensor], prefix: str):
+    """The operands of ``uf_ln_convqkv_fwd`` from ``attn.qkv.to_{q,k,v}.{depthwise,pointwise}``: the three pointwise weights (C,C,1,1) as one
+    row-major (3C, C) matrix q | k | v (not yet cast or fragment-packed), their biases f32 (3C,), the depthwise taps f32 (3, 9, C) tap-major
+    as ``pack_dwconv`` lays them out (tap = ky * 3 + kx), and the depthwise biases f32 (3, C)."""
+    g = lambda j, k: sd[prefix + f"attn.qkv.to_{j}.{k}"].detach()  # noqa: E731
+    wpw = torch.cat([g(j, "pointwise.weight").reshape(g(j, "pointwise.weight").shape[0], -1) for j in "qkv"], 0)
+    bpw = torch.cat([g(j, "pointwise.bias") for j in "qkv"], 0).contiguous().float()
+    dw9 = torch.stack([pack_dwconv(g(j, "depthwise.weight")) for j in "qkv"], 0).contiguous()
+    bdw = torch.stack([g(j, "depthwise.bias").float() for j in "qkv"], 0).contiguous()
+    return wpw, bpw, dw9, bdw
+
+
 def pack_downsample(w: Tensor, dtype: torch.dtype) -> Tensor:
     """Conv2d weight (2C,C,4,4) -> (2C, 16C) with k = (ky*4+kx)*C + c."""
     return w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous().to(dtype)
@@ -99,13 +116,18 @@ def pack_block(sd: Dict[str, Tensor], prefix: str, heads: int, shift: int, dtype
     # (p.data = ..., EMA swaps) until the owner notices the new (data_ptr, _version) key and repacks
     f = lambda k: sd[prefix + k].detach().float().clone().contiguous()  # noqa: E731
     t = lambda k: sd[prefix + k].detach().to(dtype, copy=True).contiguous()  # noqa: E731
-    wqkv = torch.cat([sd[prefix + "attn.qkv.to_q.weight"].detach(), sd[prefix + "attn.qkv.to_kv.weight"].detach()], 0)
+    conv = conv_projection_keys(sd, prefix)
+    if conv:      # ConvProjection (token_projection 'conv'): the three pointwise convolutions in the q | k | v slots, the depthwise taps beside them
+        wqkv, bqkv, dw9, bdw = pack_conv_projection(sd, prefix)
+    else:
+        wqkv = torch.cat([sd[prefix + "attn.qkv.to_q.weight"].detach(), sd[prefix + "attn.qkv.to_kv.weight"].detach()], 0)
+        bqkv = torch.cat([sd[prefix + "attn.qkv.to_q.bias"].detach(), sd[prefix + "attn.qkv.to_kv.bias"].detach()], 0).contiguous().float()
     dense = rpb_dense(sd[prefix + "attn.relative_position_bias_table"], sd[prefix + "attn.relative_position_index"])
     keep: Dict[str, Tensor] = {
         "norm1_w": f("norm1.weight"), "norm1_b": f("norm1.bias"),
         "rpb_dense": dense,
         "wqkv_fm": pack_frag(wqkv, dtype),
-        "bqkv": torch.cat([sd[prefix + "attn.qkv.to_q.bias"].detach(), sd[prefix + "attn.qkv.to_kv.bias"].detach()], 0).contiguous().float(),
+        "bqkv": bqkv,
         "wproj": t("attn.proj.weight"), "wproj_fm": pack_frag(sd[prefix + "attn.proj.weight"], dtype), "bproj": f("attn.proj.bias"),
         "norm2_w": f("norm2.weight"), "norm2_b": f("norm2.bias"),
     }
@@ -116,6 +138,8 @@ def pack_block(sd: Dict[str, Tensor], prefix: str, heads: int, shift: int, dtype
         keep.update({"w1_fm": pack_frag(sd[prefix + "mlp.linear1.0.weight"], dtype), "b1": f("mlp.linear1.0.bias"),
                      "wdw9": pack_dwconv(sd[prefix + "mlp.dwconv.0.weight"]), "bdw": f("mlp.dwconv.0.bias"),
                      "w2_fm": pack_frag(sd[prefix + "mlp.linear2.0.weight"], dtype), "b2": f("mlp.linear2.0.bias")})
+    if conv:
+        keep.update({"qkv_dw9": dw9, "qkv_bdw": bdw})
     if (prefix + "modulator.weight") in sd:
         keep["modulator"] = f("modulator.weight")
     tab = pack_rpb_table(dense)
@@ -133,6 +157,8 @@ def pack_block(sd: Dict[str, Tensor], prefix: str, heads: int, shift: int, dtype
 
 def pack_block4(sd: Dict[str, Tensor], prefix: str, heads: int, dtype: torch.dtype):
     """``uf_block4_params`` of a 4x4-window block (row-major T weights, the (heads, 49) bias table): returns (Block4Params, keepalive)."""
+    if conv_projection_keys(sd, prefix):
+        raise NotImplementedError("token_projection='conv' is not built for 4x4-window blocks (the bottleneck of an img_size-64 model)")
     if (prefix + "mlp.fc1.weight") in sd:
         raise NotImplementedError("token_mlp='ffn' is not built for 4x4-window blocks (the bottleneck of an img_size-64 model)")
     if (prefix + "modulator.weight") in sd:

@@ -33,6 +33,7 @@ class UformerConfig:
     modulator: bool = False
     shift_flag: bool = True
     token_mlp: str = "leff"      # 'leff' (LeFF) or 'ffn' / 'mlp' (Mlp: fc1 -> GELU -> fc2, model.py:890-893)
+    token_projection: str = "linear"   # 'linear' (LinearProjection) or 'conv' (ConvProjection: three SepConv2d per window, model.py:381-410)
 
     def mlp_is_ffn(self) -> bool:
         return self.token_mlp in ("ffn", "mlp")
@@ -113,10 +114,12 @@ def arch_config(name: str, img_size: int = 256, dd_in: int = 3) -> UformerConfig
 
 # ---- state_dict layout ------------------------------------------------------------------
 def block_spec(prefix: str, C: int, heads: int, win: int, modulator: bool,
-               mlp_ratio: float = 4.0, mod_win: int = None, token_mlp: str = "leff") -> Iterator[Tuple[str, Tuple[int, ...], str]]:
+               mlp_ratio: float = 4.0, mod_win: int = None, token_mlp: str = "leff",
+               token_projection: str = "linear") -> Iterator[Tuple[str, Tuple[int, ...], str]]:
     """(key, shape, kind) of one LeWinTransformerBlock, in registration order.  ``win``: the block's (clamped) window;
     ``mod_win`` (default ``win``): the unclamped window the modulator embedding is sized by (model.py:868-869);
-    ``token_mlp``: 'leff', or 'ffn' / 'mlp' for the reference's Mlp (``mlp.fc1`` / ``mlp.fc2``, model.py:623-631)."""
+    ``token_mlp``: 'leff', or 'ffn' / 'mlp' for the reference's Mlp (``mlp.fc1`` / ``mlp.fc2``, model.py:623-631);
+    ``token_projection``: 'linear', or 'conv' for the reference's ConvProjection (``attn.qkv.to_{q,k,v}.{depthwise,pointwise}``, model.py:344-392)."""
     hid = int(C * mlp_ratio)
     if modulator:
         mw = win if mod_win is None else mod_win
@@ -125,10 +128,17 @@ def block_spec(prefix: str, C: int, heads: int, win: int, modulator: bool,
     yield prefix + "norm1.bias", (C,), "ln_b"
     yield prefix + "attn.relative_position_bias_table", ((2 * win - 1) ** 2, heads), "rpb"
     yield prefix + "attn.relative_position_index", (win * win, win * win), "rpi"
-    yield prefix + "attn.qkv.to_q.weight", (C, C), "linear_w"
-    yield prefix + "attn.qkv.to_q.bias", (C,), "linear_b"
-    yield prefix + "attn.qkv.to_kv.weight", (2 * C, C), "linear_w"
-    yield prefix + "attn.qkv.to_kv.bias", (2 * C,), "linear_b"
+    if token_projection == "conv":
+        for j in "qkv":
+            yield prefix + f"attn.qkv.to_{j}.depthwise.weight", (C, 1, 3, 3), "conv_w"
+            yield prefix + f"attn.qkv.to_{j}.depthwise.bias", (C,), "conv_b"
+            yield prefix + f"attn.qkv.to_{j}.pointwise.weight", (C, C, 1, 1), "conv_w"
+            yield prefix + f"attn.qkv.to_{j}.pointwise.bias", (C,), "conv_b"
+    else:
+        yield prefix + "attn.qkv.to_q.weight", (C, C), "linear_w"
+        yield prefix + "attn.qkv.to_q.bias", (C,), "linear_b"
+        yield prefix + "attn.qkv.to_kv.weight", (2 * C, C), "linear_w"
+        yield prefix + "attn.qkv.to_kv.bias", (2 * C,), "linear_b"
     yield prefix + "attn.proj.weight", (C, C), "linear_w"
     yield prefix + "attn.proj.bias", (C,), "linear_b"
     yield prefix + "norm2.weight", (C,), "ln_w"
@@ -161,7 +171,8 @@ def state_dict_spec(cfg: UformerConfig) -> List[Tuple[str, Tuple[int, ...], str]
     def stage(s: int):
         for i in range(cfg.depths[s]):
             spec.extend(block_spec(f"{STAGES[s]}.blocks.{i}.", dims[s], cfg.num_heads[s],
-                                   wins[s], cfg.stage_has_modulator(s), cfg.mlp_ratio, mod_win=cfg.win_size, token_mlp=cfg.token_mlp))
+                                   wins[s], cfg.stage_has_modulator(s), cfg.mlp_ratio, mod_win=cfg.win_size, token_mlp=cfg.token_mlp,
+                                   token_projection=cfg.token_projection))
 
     for s in range(4):
         stage(s)

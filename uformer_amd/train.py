@@ -53,6 +53,7 @@ class BlockPack:
 
     def __init__(self, p: Dict[str, Tensor], prefix: str, heads: int, shift: int, T: torch.dtype, fused: bool):
         f = lambda k: p[prefix + k]                                             # noqa: E731
+        refuse_conv_projection(p, prefix)
         self.prefix, self.heads, self.shift, self.T = prefix, heads, shift, T
         self.win = block_window(p, prefix)
         self.rpb4 = None
@@ -120,6 +121,7 @@ class NativeBlockPack:
 
     def __init__(self, p: Dict[str, Tensor], prefix: str, heads: int, shift: int, T: torch.dtype):
         from . import _lib
+        refuse_conv_projection(p, prefix)
         self.prefix, self.heads, self.shift, self.T = prefix, heads, shift, T
         f = lambda k: p[prefix + k].detach()                                   # noqa: E731
         names = dict(norm1_w="norm1.weight", norm1_b="norm1.bias", norm2_w="norm2.weight", norm2_b="norm2.bias", rpb_table="attn.relative_position_bias_table",
@@ -208,6 +210,16 @@ def block_window(p: Dict[str, Tensor], prefix: str = "") -> int:
     if (2 * win - 1) ** 2 != n or win not in (4, 8):
         raise ops.UformerHipError(f"{prefix}attn.relative_position_bias_table has {n} rows: windows 8 (225) and 4 (49) are built")
     return win
+
+
+TOKEN_PROJECTION_TRAINING = ("token_projection='conv' runs inference only: training (autograd, the training tape, use_checkpoint) has no backward for "
+                             "the ConvProjection yet; run it in eval() under torch.no_grad()")
+
+
+def refuse_conv_projection(p: Dict[str, Tensor], prefix: str = "") -> None:
+    """Training packs are built for the LinearProjection; a ConvProjection block (told by its parameter names) is refused by name."""
+    if packing.conv_projection_keys(p, prefix):
+        raise NotImplementedError(TOKEN_PROJECTION_TRAINING)
 
 
 def block_is_mlp(p: Dict[str, Tensor], prefix: str = "") -> bool:
@@ -595,6 +607,8 @@ class UformerTape:
     def __init__(self, sd: Dict[str, Tensor], cfg, dtype: torch.dtype = torch.float32, drop_scales: Optional[Tensor] = None,
                  recompute: Optional[bool] = None, on_stage_done=None):
         self.sd, self.cfg, self.T, self.drop = sd, cfg, dtype, drop_scales
+        if getattr(cfg, "token_projection", "linear") != "linear":
+            raise NotImplementedError(TOKEN_PROJECTION_TRAINING)
         if recompute is None and os.environ.get("UF_TRAIN_RECOMPUTE") is not None:       # A/B switch: 0 = keep every intermediate, 1 = always recompute
             recompute = os.environ["UF_TRAIN_RECOMPUTE"] != "0"
         # None = decided in forward() from the batch and the free device memory (2-byte operand types; f32 always keeps its intermediates)
