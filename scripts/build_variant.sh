@@ -1,7 +1,8 @@
 #!/bin/bash
 # A/B builds: scripts/build_variant.sh <name> <sed-expr> <file.hip> [<sed-expr> <file.hip> ...]
 # compiles patched copies of the named sources (everything else reuses uformer_amd/lib/*.o) into ab/<name>/libuformer_hip.so;
-# select it at run time with UFORMER_HIP_LIB=ab/<name>/libuformer_hip.so.
+# select it at run time with UFORMER_HIP_LIB=ab/<name>/libuformer_hip.so.  The source list and the per-file flags are build()'s
+# (__graft_entry__.SOURCES / EXTRA_FLAGS), so a variant differs from the shipped library in the patch alone.
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd); name=$1; shift
 out=$R/ab/$name; mkdir -p $out; objs=""
@@ -11,13 +12,13 @@ while [ $# -ge 2 ]; do
     src=$out/$f; [ -f $src ] || cp $R/uformer_amd/csrc/$f $src
     sed -i "$expr" $src; patched[$f]=1
 done
-for f in uf_core uf_gemm uf_lngemm uf_leff2 uf_attnblk uf_attn uf_elementwise uf_bwd uf_train uf_trainblk uf_pack uf_model; do
-    if [ -n "${patched[$f.hip]}" ]; then
-        sed -i "s|#include \"uf_internal.h\"|#include \"$R/uformer_amd/csrc/uf_internal.h\"|; s|#include \"uf_common.h\"|#include \"$R/uformer_amd/csrc/uf_common.h\"|" $out/$f.hip
-        /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c $out/$f.hip -o $out/$f.o
-        objs="$objs $out/$f.o"
+for f in $(cd $R && python -c "import __graft_entry__ as g; print(' '.join(g.SOURCES))"); do
+    if [ -n "${patched[$f]}" ]; then
+        extra=$(cd $R && python -c "import sys, __graft_entry__ as g; print(' '.join(g.EXTRA_FLAGS.get(sys.argv[1], [])))" $f)
+        /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $extra -I$R/uformer_amd/csrc -c $out/$f -o $out/${f%.hip}.o    # -I: the copy's "uf_*.h" includes
+        objs="$objs $out/${f%.hip}.o"
     else
-        objs="$objs $R/uformer_amd/lib/$f.o"
+        objs="$objs $R/uformer_amd/lib/${f%.hip}.o"
     fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libuformer_hip.so $objs

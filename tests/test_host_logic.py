@@ -227,3 +227,17 @@ def test_restore_tiled_seams_are_exact_for_a_pointwise_model():
         assert got.shape == img.shape and all(c[-1] == tile and c[-2] == tile for c in calls)
         assert (got - pointwise(img)).abs().max().item() < 2e-6, (h, w, tile)
         assert len(calls) > 1
+
+
+def test_no_compile_time_switches_in_csrc():
+    """The kernel sources carry only what ships: no `#ifndef UF_X / #define UF_X` experiment switch and no `#if UF_X` arm."""
+    import glob
+    import os
+    import re
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "uformer_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert files
+    switch = re.compile(r"^#\s*ifn?def\s+UF_|^#\s*if\s+UF_")
+    hits = [f"{os.path.basename(f)}:{n}: {line.rstrip()}" for f in files for n, line in enumerate(open(f), 1) if switch.search(line)]
+    assert not hits, ("compile-time experiment switches in uformer_amd/csrc -- keep the experiment in an A/B copy (scripts/build_variant.sh) "
+                      "and land only the winner:\n" + "\n".join(hits))

@@ -53,58 +53,15 @@ struct AttnBlkParams {
 constexpr float LOG2E = 1.4426950408889634f;
 
 // weight-fragment ring depths (k-steps of L2 -> register loads in flight) of the three GEMM phases at C >= 256
-#ifndef UF_P1_OFFSET
-#define UF_P1_OFFSET 0
-#endif
-#ifndef UF_FC1_OFFSET
-#define UF_FC1_OFFSET 0
-#endif
-#ifndef UF_STAGGER
-#define UF_STAGGER 0
-#endif
-#ifndef UF_SETPRIO
-#define UF_SETPRIO 0
-#endif
-#define UF_PRIO_UP() do { if (UF_SETPRIO) __builtin_amdgcn_s_setprio(1); } while (0)
-#define UF_PRIO_DN() do { if (UF_SETPRIO) __builtin_amdgcn_s_setprio(0); } while (0)
-#ifndef UF_ABL
-#define UF_ABL 0   // ablations for profiling (1: no x loads, 2: no LN math, 3: no modulator loads, 4: no h1 stores, 5: no row stores in phase 2, 6: no weight-fragment loads in any GEMM phase, 7: no LDS operand-fragment loads, 8: no GELU in phase 3, 9: no softmax arithmetic); 0 in every shipped build
-#endif
-// UF_NT (experiment, bit mask): non-temporal hints on the activation streams so that they do not evict the block's weights (4 MB at C = 512 = one
-// XCD's whole L2) -- 1: h1 stores, 2: the new x rows of phase 2, 4: the x loads of phase 0
-#ifndef UF_NT
-#define UF_NT 0
-#endif
-#ifndef UF_LN_ROTATE
-#define UF_LN_ROTATE 0
-#endif
-#ifndef UF_LN_WIDE
-#define UF_LN_WIDE 1
-#endif
-#ifndef UF_QKV_RING
-#define UF_QKV_RING 3
-#endif
-#ifndef UF_PROJ_RING
-#define UF_PROJ_RING 3
-#endif
-#ifndef UF_FC1_RING
-#define UF_FC1_RING 5
-#endif
-// UF_HOIST: the first weight fragments of a GEMM phase are requested BEFORE the phase in front of it (q/k/v weights before the LayerNorm
+constexpr int QKV_RING = 3, PROJ_RING = 3, FC1_RING = 5;
+// Hoisting: the first weight fragments of a GEMM phase are requested BEFORE the phase in front of it (q/k/v weights before the LayerNorm
 // of phase 0, the next unit's right behind the current unit's last MFMA, proj weights + residual rows in front of the barrier that ends
 // phase 1, fc1 weights in front of LN2): at C <= 128 a phase is 2-4 k-steps long, so the L2 round trip of its first fragments was as
 // long as the phase itself and nothing hid it; fc1 weights are also requested in front of the row stores of phase 2 (vector memory
 // returns in order and the counter covers stores: fragments requested behind the store burst wait for its last ack).  Bit-identical
-// results (same MFMAs on the same operands).  Bit mask of widths it is on for: 1: C <= 128, 2: C = 256, 4: C = 512.  Measured
-// (profiles/r03_hoist2_ab.txt, four interleaved rounds): attn_block 3.98 -> 3.88 ms per step with every width on (7), the default.
-#ifndef UF_HOIST
-#define UF_HOIST 7
-#endif
-template <int C> constexpr bool hoist_on() { return (C <= 128 && (UF_HOIST & 1)) || (C == 256 && (UF_HOIST & 2)) || (C == 512 && (UF_HOIST & 4)); }
+// results (same MFMAs on the same operands).  Measured (profiles/r03_hoist2_ab.txt, four interleaved rounds): attn_block 3.98 -> 3.88 ms
+// per step with every width hoisting.
 
-#ifndef UF_ATTN_LR_DEFAULT
-#define UF_ATTN_LR_DEFAULT 0
-#endif
 template <typename T> struct FragFromAcc {   // primary: the 2-byte operand types
     static __device__ __forceinline__ void make(Frag<T>& f, f32x4 a, f32x4 b) {
         f.v = u32x4{pack2<T>(a[0], a[1]), pack2<T>(a[2], a[3]), pack2<T>(b[0], b[1]), pack2<T>(b[2], b[3])};
@@ -113,16 +70,6 @@ template <typename T> struct FragFromAcc {   // primary: the 2-byte operand type
 template <> struct FragFromAcc<float> {
     static __device__ __forceinline__ void make(Frag<float>& f, f32x4 a, f32x4 b) { f.lo = a; f.hi = b; }
 };
-
-// weight / operand fragment loads of the GEMM phases, with the timing ablations 6 / 7 (registers filled from the lane id instead of memory)
-template <typename T> __device__ __forceinline__ void wfrag_load(Frag<T>& f, const T* p) {
-    if constexpr (UF_ABL == 6 && sizeof(T) == 2) { const unsigned v = 0x3c003c00u ^ (unsigned)(uintptr_t)p; f.v = u32x4{v, v, v, v}; }
-    else load_frag(f, p);
-}
-template <typename T> __device__ __forceinline__ void afrag_load(Frag<T>& f, const T* p) {
-    if constexpr (UF_ABL == 7 && sizeof(T) == 2) { const unsigned v = 0x3c003c00u ^ (unsigned)(uintptr_t)p; f.v = u32x4{v, v, v, v}; }
-    else load_frag(f, p);
-}
 
 // A fragment made from accumulators is COMPUTED HERE (ST form): the IR-level sinking passes otherwise move the bias add + pack down to the first use
 // across the sched_barriers -- the f32 accumulators (twice the registers) then stay alive through the next projection and spill under the 168-register bound
@@ -143,19 +90,19 @@ template <int N> __device__ __forceinline__ float tree_sum(float* v) {   // bala
 // LDS: the barrier-free 64 x 64 unit walk of ln_gemm (uf_lngemm.hip) -- fragment-major weights streamed L2 -> registers
 // through a 3-deep ring pinned with sched_barrier, first k-steps of the next unit issued before the epilogue, and the
 // permlane-widened direct 16-byte stores.  2-byte operand types only.
-// Fc1Walk::first(): the weight fragments of the wave's first unit (callable before the operand tile exists: UF_HOIST);
+// Fc1Walk::first(): the weight fragments of the wave's first unit (callable before the operand tile exists: hoisting, above);
 // Fc1Walk::run(): the walk.
 template <typename T, int C, int WAVES, int UW = 4, bool ACT = true>   // ACT = false: the pre-activation is stored (training: the backward needs GELU'(a1))
 struct Fc1Walk {
     static_assert(UW == 4 || UW == 2, "units of 64 x 64 or 64 x 32");
-    static constexpr int SZ = sizeof(T), KS = C / 32, RING = KS >= 8 ? UF_FC1_RING : (KS >= 4 ? 4 : 3), N4 = 4 * C, UNITS = N4 / (16 * UW);
+    static constexpr int SZ = sizeof(T), KS = C / 32, RING = KS >= 8 ? FC1_RING : (KS >= 4 ? 4 : 3), N4 = 4 * C, UNITS = N4 / (16 * UW);
     const T* wrow[UW];
     Frag<T> wf[RING][UW];
     const T* W1;
     int lane;
     __device__ __forceinline__ void wload(int ks, int slot) {
 #pragma unroll
-        for (int i = 0; i < UW; ++i) wfrag_load(wf[slot][i], wrow[i] + ks * 512);
+        for (int i = 0; i < UW; ++i) load_frag(wf[slot][i], wrow[i] + ks * 512);
     }
     __device__ __forceinline__ void unit_prefetch(int u) {
 #pragma unroll
@@ -176,7 +123,6 @@ struct Fc1Walk {
     size_t rowoff[4];   // h1 row of this lane's token in each 16-row tile (window_reverse + roll back, as the residual rows)
 #pragma unroll
     for (int j = 0; j < 4; ++j) rowoff[j] = (size_t)window_token(geo, j * 16 + fr) * N4;
-    if (WAVES == 8 && UF_FC1_OFFSET > 0 && wave >= 4) __builtin_amdgcn_s_sleep(UF_FC1_OFFSET * (C / 256) > 127 ? 127 : UF_FC1_OFFSET * (C / 256));   // as in phase 1
 #pragma unroll 1
     for (int u = wave; u < UNITS; u += WAVES) {
         const int nbase = u * 16 * UW;
@@ -189,7 +135,7 @@ struct Fc1Walk {
         Frag<T> af[2][4];
         auto aload = [&](int ks, int slot) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) afrag_load(af[slot][j], reinterpret_cast<const T*>(arow + j * 16 * SA + ks * 32 * SZ));
+            for (int j = 0; j < 4; ++j) load_frag(af[slot][j], reinterpret_cast<const T*>(arow + j * 16 * SA + ks * 32 * SZ));
         };
         aload(0, 0);
         f32x4 bv[UW];   // the unit's bias: requested here, consumed after the k-loop (was an exposed L2 round trip per unit)
@@ -200,12 +146,10 @@ struct Fc1Walk {
             if (ks + RING - 1 < KS) wload(ks + RING - 1, (ks + RING - 1) % RING);
             if (ks + 1 < KS) aload(ks + 1, (ks + 1) & 1);
             __builtin_amdgcn_sched_barrier(0);
-            UF_PRIO_UP();
 #pragma unroll
             for (int i = 0; i < UW; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) mma16(acc[i][j], wf[ks % RING][i], af[ks & 1][j]);   // weight as A: lane = 4 channels of one token
-            UF_PRIO_DN();
             __builtin_amdgcn_sched_barrier(0);
         }
         if (u + WAVES < UNITS) unit_prefetch(u + WAVES);
@@ -215,15 +159,13 @@ struct Fc1Walk {
 #pragma unroll
             for (int ip = 0; ip < UW; ip += 2) {
                 f32x4 va = acc[ip][j] + bv[ip], vb = acc[ip + 1][j] + bv[ip + 1];
-                if (UF_ABL != 8 && ACT) { gelu4<T>(va); gelu4<T>(vb); }
+                if (ACT) { gelu4<T>(va); gelu4<T>(vb); }
                 const unsigned a0 = pack2<T>(va[0], va[1]), a1 = pack2<T>(va[2], va[3]);
                 const unsigned c0 = pack2<T>(vb[0], vb[1]), c1 = pack2<T>(vb[2], vb[3]);
                 const u32x2_t s0 = __builtin_amdgcn_permlane16_swap(a0, c0, false, false);
                 const u32x2_t s1 = __builtin_amdgcn_permlane16_swap(a1, c1, false, false);
                 const int n = nbase + (ip + (fg & 1)) * 16 + (fg >> 1) * 8;
-                if (UF_ABL == 4) asm volatile("" :: "v"(s0[0]), "v"(s1[0]), "v"(s0[1]), "v"(s1[1]), "v"(h1 + rowoff[j] + n));   // ablation: no h1 stores
-                else if (UF_NT & 1) __builtin_nontemporal_store(u32x4{s0[0], s1[0], s0[1], s1[1]}, reinterpret_cast<u32x4*>(h1 + rowoff[j] + n));
-                else *reinterpret_cast<u32x4*>(h1 + rowoff[j] + n) = u32x4{s0[0], s1[0], s0[1], s1[1]};
+                *reinterpret_cast<u32x4*>(h1 + rowoff[j] + n) = u32x4{s0[0], s1[0], s0[1], s1[1]};
             }
         }
     }
@@ -295,10 +237,6 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
     };
     stamp(0);
     Census census; census.begin();
-    if (UF_STAGGER > 0 && ((blockIdx.x >> 8) & 1)) {      // experiment: offset the second resident workgroup of a CU by UF_STAGGER x 8 K cycles
-#pragma unroll
-        for (int k = 0; k < UF_STAGGER; ++k) __builtin_amdgcn_s_sleep(127);
-    }
 
     // The small tables of the later phases (relative-position bias, q/k/v and proj biases) are REQUESTED here, all at once and
     // unconditionally (clamped index), and stored to LDS after phase 0.  They used to be copied by a load -> store loop behind
@@ -312,21 +250,21 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
         const float* src = i < HEADS * 225 ? p.rpb_tab + i : (i < HEADS * 225 + 3 * C ? p.bqkv + (i - HEADS * 225) : p.bp + (i - HEADS * 225 - 3 * C));
         tabv[k] = *src;
     }
-    // q/k/v weight ring of phase 1 (k-steps of L2 -> register loads in flight) and the first unit's prologue, see UF_HOIST
-    constexpr bool HOIST = hoist_on<C>() && SZ == 2;      // (the f32 parity variants have no registers to spare)
-    constexpr int WR = (SZ == 2 && C >= 256) ? UF_QKV_RING : ((SZ == 2 && C >= 128) ? 3 : 2);
+    // q/k/v weight ring of phase 1 (k-steps of L2 -> register loads in flight) and the first unit's prologue (hoisting, see the top of the file)
+    constexpr bool HOIST = SZ == 2;      // every 2-byte width hoists; the f32 parity variants have no registers to spare
+    constexpr int WR = (SZ == 2 && C >= 256) ? QKV_RING : ((SZ == 2 && C >= 128) ? 3 : 2);
     const T* Wqkv = reinterpret_cast<const T*>(p.Wqkv);
     const T* wrow[6];
     Frag<T> wf[WR][LR ? 2 : 6];
     auto wload = [&](int ks, int slot) {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) wfrag_load(wf[slot][i], wrow[i] + ks * 512);
+        for (int i = 0; i < 6; ++i) load_frag(wf[slot][i], wrow[i] + ks * 512);
     };
     // LR: step g of the flattened walk = (projection g / KS in the order k, v, q; k-step g % KS): two fragments
     auto wload2 = [&](int g, int slot) {
         const int pj = g / KS, ks = g - pj * KS, base = pj == 0 ? 2 : (pj == 1 ? 4 : 0);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) wfrag_load(wf[slot][i], wrow[base + i] + ks * 512);
+        for (int i = 0; i < 2; ++i) load_frag(wf[slot][i], wrow[base + i] + ks * 512);
     };
     auto unit_weights = [&](int u) {   // 16-row weight tiles of the unit's head in the fragment-major Wqkv (q tiles h*2+i, k tiles C/16+.., v tiles 2C/16+..) + ring prologue
         const int h = u / (4 / QT);
@@ -347,7 +285,7 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
         // cross-lane reductions, the square root and the division -- is what this phase spends its VALU time on (measured:
         // 27 K cycles at C = 256 with 64 lanes x 4 channels per row, against 4 K for the loads alone), and it is paid per lane:
         // 16 lanes x 16 channels cut the rows a thread owns from 16 to 4 and each reduction from 6 steps to 4.
-        constexpr int LPR = UF_LN_WIDE ? ((C / 16) < 8 ? 8 : (C / 16)) : ((C / 4) < 64 ? (C / 4) : 64);
+        constexpr int LPR = (C / 16) < 8 ? 8 : (C / 16);
         constexpr int V4 = C / (4 * LPR);
         constexpr int RPP = NT / LPR;
         constexpr int NP = 64 / RPP;
@@ -355,30 +293,23 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
         constexpr int U = (ST && U0 > 2) ? 2 : U0;            // ST: half the rows per pass (x and modulator rows of a pass: 128 -> 64 registers)
         static_assert(NP >= 1 && NP % U == 0, "pass batching");
         const int sub = tid % LPR;
-        // the order in which a workgroup walks its rows is rotated by the window index: all workgroups start together, and with
-        // one fixed order the addresses requested at any moment differ only in the window bits (several address bits are the
-        // same chip-wide -> the requests of a round pile up on a subset of the memory channels)
-        static_assert((U & (U - 1)) == 0, "U is a power of two");
-        const int rot = UF_LN_ROTATE ? bw : 0;
 #pragma unroll 1
         for (int r0 = 0; r0 < 64; r0 += RPP * U) {
             f32x4 v[U][V4], md[U][V4];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const int src = window_token(geo, r0 + ((u + rot) & (U - 1)) * RPP + tid / LPR);
+                const int src = window_token(geo, r0 + u * RPP + tid / LPR);
 #pragma unroll
                 for (int i = 0; i < V4; ++i) {
-                    if (UF_ABL == 1) v[u][i] = f32x4{(float)src, (float)i, (float)sub, 1.0f};   // ablation: no x loads
-                    else if (UF_NT & 4) v[u][i] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p.x + (size_t)src * p.ld + (i * LPR + sub) * 4));
-                    else v[u][i] = *reinterpret_cast<const f32x4*>(p.x + (size_t)src * p.ld + (i * LPR + sub) * 4);
+                    v[u][i] = *reinterpret_cast<const f32x4*>(p.x + (size_t)src * p.ld + (i * LPR + sub) * 4);
                 }
             }
             // the modulator rows of the same tokens, requested together with x: read inside the normalisation loop they were
             // 16 dependent L2 round trips per thread (ablation: 11 K of the 23 K cycles of this phase at C = 256, 14 K at C = 512)
-            if (p.modulator && UF_ABL != 3) {
+            if (p.modulator) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    const int row = r0 + ((u + rot) & (U - 1)) * RPP + tid / LPR;
+                    const int row = r0 + u * RPP + tid / LPR;
 #pragma unroll
                     for (int i = 0; i < V4; ++i) md[u][i] = *reinterpret_cast<const f32x4*>(p.modulator + (size_t)row * C + (i * LPR + sub) * 4);
                 }
@@ -396,7 +327,7 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const int row = r0 + ((u + rot) & (U - 1)) * RPP + tid / LPR;
+                const int row = r0 + u * RPP + tid / LPR;
                 float sum = 0.f;
 #pragma unroll
                 for (int i = 0; i < V4; ++i) sum += (v[u][i][0] + v[u][i][1]) + (v[u][i][2] + v[u][i][3]);
@@ -416,7 +347,6 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
                 for (int i = 0; i < V4; ++i) {
                     const int c = (i * LPR + sub) * 4;
                     f32x4 y = v[u][i] * rstd * gm[i] + bt[i] + md[u][i];      // + modulator (model.py:966-969), zeros in the encoder
-                    if (UF_ABL == 2) y = v[u][i];                             // ablation: no LN math
                     store4(reinterpret_cast<T*>(Xn + row * SA) + c, y);
                 }
             }
@@ -450,10 +380,6 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
     const bool last_c = p.shift > 0 && (wi % nWc) == nWc - 1;
 
     // ---------------- phase 1: per-unit QKV projection + attention, all in registers -------------------
-    // 8-wave workgroups put TWO of their waves on every SIMD, and the barriers keep them in lockstep: both fight for the matrix
-    // pipe during the projections, then both leave it idle during the softmax.  Holding back the second half of the waves by about
-    // one projection lets a SIMD run one wave's MFMAs beside the other's VALU work (UF_P1_OFFSET x 64 cycles, 0 = off).
-    if (WAVES == 8 && UF_P1_OFFSET > 0 && wave >= 4) __builtin_amdgcn_s_sleep(UF_P1_OFFSET * (C / 256) > 127 ? 127 : UF_P1_OFFSET * (C / 256));
     constexpr int UPW = (UNITS + WAVES - 1) / WAVES;             // units per wave
     static_assert(!ST || (SZ == 2 && UNITS % WAVES == 0), "single-tile form: 2-byte operands, every wave owns the same number of heads");
     unsigned opk[ST ? UPW : 1][QT][4];                           // ST: the finished heads of this wave, packed, until Xn may be overwritten
@@ -462,16 +388,16 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
         Frag<T> qf[QT], kf[4], vtf[2][2];
         if constexpr (LR) {
             // ---- low-register form: k, then v, then q; the ring runs across the three projections (3 KS steps) ----
-            if constexpr (!HOIST) unit_weights(u);
+            static_assert(!LR || HOIST, "low-register form: 2-byte operand types");
             Frag<T> af[2][4];
             auto aload2 = [&](int g, int slot) {      // activation fragments of step g: all four row tiles (k, v) or the unit's query tiles (q)
                 const int pj = g / KS, ks = g - pj * KS;
                 if (pj < 2 || QT == 4) {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) afrag_load(af[slot][j], reinterpret_cast<const T*>(Xn + (j * 16 + fr) * SA + (ks * 32 + fg * 8) * SZ));
+                    for (int j = 0; j < 4; ++j) load_frag(af[slot][j], reinterpret_cast<const T*>(Xn + (j * 16 + fr) * SA + (ks * 32 + fg * 8) * SZ));
                 } else {
 #pragma unroll
-                    for (int j = 0; j < QT; ++j) afrag_load(af[slot][j], reinterpret_cast<const T*>(Xn + ((q0 + j) * 16 + fr) * SA + (ks * 32 + fg * 8) * SZ));
+                    for (int j = 0; j < QT; ++j) load_frag(af[slot][j], reinterpret_cast<const T*>(Xn + ((q0 + j) * 16 + fr) * SA + (ks * 32 + fg * 8) * SZ));
                 }
             };
             aload2(0, 0);
@@ -542,9 +468,7 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 if (u == wave) stamp(3);
-                if constexpr (HOIST) {
-                    if (u + WAVES < UNITS) unit_weights(u + WAVES);
-                }
+                if (u + WAVES < UNITS) unit_weights(u + WAVES);
                 const f32x4 bq0 = *reinterpret_cast<const f32x4*>(Bq + h * 32 + fg * 4), bq1 = *reinterpret_cast<const f32x4*>(Bq + h * 32 + 16 + fg * 4);
 #pragma unroll
                 for (int j = 0; j < QT; ++j) FragFromAcc<T>::make(qf[j], (aq[0][j] + bq0) * p.qscale, (aq[1][j] + bq1) * p.qscale);
@@ -565,11 +489,11 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
         if constexpr (!HOIST) unit_weights(u);
         auto aload = [&](int ks, int slot) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) afrag_load(af[slot][j], reinterpret_cast<const T*>(Xn + (j * 16 + fr) * SA + (ks * 32 + fg * 8) * SZ));
+            for (int j = 0; j < 4; ++j) load_frag(af[slot][j], reinterpret_cast<const T*>(Xn + (j * 16 + fr) * SA + (ks * 32 + fg * 8) * SZ));
             if constexpr (QT < 4) {
 #pragma unroll
                 for (int j = 0; j < QT; ++j)
-                    afrag_load(afq[slot][j], reinterpret_cast<const T*>(Xn + ((q0 + j) * 16 + fr) * SA + (ks * 32 + fg * 8) * SZ));
+                    load_frag(afq[slot][j], reinterpret_cast<const T*>(Xn + ((q0 + j) * 16 + fr) * SA + (ks * 32 + fg * 8) * SZ));
             }
         };
         aload(0, 0);
@@ -579,7 +503,6 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
             if (ks + 1 < KS) aload(ks + 1, (ks + 1) & 1);
             __builtin_amdgcn_sched_barrier(0);
             const int s = ks & 1, sw = ks % WR;
-            UF_PRIO_UP();
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -592,7 +515,6 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
 #pragma unroll
                 for (int j = 0; j < 4; ++j) mma16(av[i][j], af[s][j], wf[sw][4 + i]);        // v: activation as A operand
             }
-            UF_PRIO_DN();
             __builtin_amdgcn_sched_barrier(0);
         }
         if (u == wave) stamp(3);
@@ -720,7 +642,7 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
             for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float e = UF_ABL == 9 ? s[kt][j][r] - mx : __builtin_amdgcn_exp2f(s[kt][j][r] - mx);
+                    const float e = __builtin_amdgcn_exp2f(s[kt][j][r] - mx);
                     s[kt][j][r] = e;
                     sum += e;
                 }
@@ -780,7 +702,7 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
         for (int u = wave; u < UNITS; u += WAVES) unit(u, 0);
     }
     stamp(5);
-    std::conditional_t<SZ == 2, Fc1Walk<T, C, WAVES, LR ? 2 : 4, TR == 0>, NoWalk> fc1w;     // phase 3's weight ring: its first fragments are requested in front of LN2 (UF_HOIST)
+    std::conditional_t<SZ == 2, Fc1Walk<T, C, WAVES, LR ? 2 : 4, TR == 0>, NoWalk> fc1w;     // phase 3's weight ring: its first fragments are requested in front of LN2 (hoisting)
     // ---------------- phase 2: proj + window_reverse + roll back + residual ---------------------------
     {
         constexpr int WN = (C / 16) < WAVES ? (C / 16) : WAVES, WM = WAVES / WN;
@@ -793,15 +715,15 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
         for (int i = 0; i < TNW; ++i)
 #pragma unroll
             for (int j = 0; j < TMW; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        constexpr int PR = SZ == 2 ? (KS >= 8 ? UF_PROJ_RING : 3) : 2;   // weight ring depth (k-steps in flight)
+        constexpr int PR = SZ == 2 ? (KS >= 8 ? PROJ_RING : 3) : 2;   // weight ring depth (k-steps in flight)
         Frag<T> wf[PR][TNW], af[2][TMW];
         auto wload = [&](int ks, int slot) {
 #pragma unroll
-            for (int i = 0; i < TNW; ++i) wfrag_load(wf[slot][i], Wp + (((size_t)(wn * TNW + i) * KS + ks) * 64 + lane) * 8);
+            for (int i = 0; i < TNW; ++i) load_frag(wf[slot][i], Wp + (((size_t)(wn * TNW + i) * KS + ks) * 64 + lane) * 8);
         };
         auto aload = [&](int ks, int slot) {
 #pragma unroll
-            for (int j = 0; j < TMW; ++j) afrag_load(af[slot][j], reinterpret_cast<const T*>(Os + ((wm * TMW + j) * 16 + fr) * SA + (ks * 32 + fg * 8) * SZ));
+            for (int j = 0; j < TMW; ++j) load_frag(af[slot][j], reinterpret_cast<const T*>(Os + ((wm * TMW + j) * 16 + fr) * SA + (ks * 32 + fg * 8) * SZ));
         };
         // the rows this wave updates: addresses now, and (2-byte operand types: registers allow it) the residual values and
         // the bias requested BEFORE the k-loop, so that their round trip (L2: the rows were read in phase 0) hides under it
@@ -828,7 +750,7 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
                 }
             }
         };
-        if constexpr (HOIST) proj_requests();      // in flight across the barrier (UF_HOIST): waves that finish phase 1 early wait there anyway
+        if constexpr (HOIST) proj_requests();      // in flight across the barrier (hoisting): waves that finish phase 1 early wait there anyway
         phase_barrier<WAVES>();
         stamp(6);
         if constexpr (TR) tile_out(Os, p.s_o, false);
@@ -839,16 +761,14 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
             if (ks + PR - 1 < KS) wload(ks + PR - 1, (ks + PR - 1) % PR);
             if (ks + 1 < KS) aload(ks + 1, (ks + 1) & 1);
             __builtin_amdgcn_sched_barrier(0);
-            UF_PRIO_UP();
 #pragma unroll
             for (int i = 0; i < TNW; ++i)
 #pragma unroll
                 for (int j = 0; j < TMW; ++j) mma16(acc[i][j], wf[ks % PR][i], af[ks & 1][j]);
-            UF_PRIO_DN();
             __builtin_amdgcn_sched_barrier(0);
         }
         stamp(7);
-        if constexpr (SZ == 2 && HOIST) {
+        if constexpr (HOIST) {
             // phase 3's first weight fragments are requested BEFORE this phase's row stores: vector memory returns in order and the
             // counter covers stores too, so fragments requested behind the 64 x C x 4-byte store burst would wait for its last ack
             if (p.h1) fc1w.first(reinterpret_cast<const T*>(p.W1), wave, lane);
@@ -864,9 +784,7 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
                 const f32x4 b = *reinterpret_cast<const f32x4*>(Bq + 3 * C + n);
                 if constexpr (PRE) acc[i][j] = res[i][j] + (acc[i][j] + b) * dscale;   // the block's new rows stay in registers
                 else acc[i][j] = *reinterpret_cast<const f32x4*>(xr + n) + (acc[i][j] + b) * dscale;
-                if (UF_ABL == 5) asm volatile("" :: "v"(acc[i][j][0]), "v"(acc[i][j][1]), "v"(acc[i][j][2]), "v"(acc[i][j][3]), "v"(xw + n));   // ablation: no row stores
-                else if (UF_NT & 2) __builtin_nontemporal_store(acc[i][j], reinterpret_cast<f32x4*>(xw + n));
-                else *reinterpret_cast<f32x4*>(xw + n) = acc[i][j];
+                *reinterpret_cast<f32x4*>(xw + n) = acc[i][j];
             }
         }
         if constexpr (SZ == 2) {
@@ -925,7 +843,6 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
             phase_barrier<WAVES>();
             stamp(11);
             if constexpr (TR) tile_out(Xn, p.s_z, true);
-            if constexpr (!HOIST) fc1w.first(reinterpret_cast<const T*>(p.W1), wave, lane);
             fc1w.run(Xn, SA, p.b1, reinterpret_cast<T*>(p.h1), geo, wave);
             stamp(12);
         }

@@ -1469,9 +1469,7 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(const T* __restric
 // Same products, the same softmax algebra; the order of the 32-deep / 64-deep sums inside an MFMA chain is the hardware's in both versions:
 // results agree with the first version to operand rounding (tests/test_gpu_bwd.py compares both with the oracle).
 // ---------------------------------------------------------------------------------------------------------------
-#ifndef UF_ATTN_BWD2_WPS
-#define UF_ATTN_BWD2_WPS 2      // waves per SIMD the kernel is bounded for: 3 (168 registers) spills 11 dwords and measured 2374 us over the nine stage shapes against 1777 at 2 (profiles/r04_run9.txt)
-#endif
+constexpr int ATTN_BWD2_WPS = 2;   // waves per SIMD the kernel is bounded for: 3 (168 registers) spills 11 dwords and measured 2374 us over the nine stage shapes against 1777 at 2 (profiles/r04_run9.txt)
 __device__ __forceinline__ u32x4 tr_frag(unsigned a0, unsigned a1) {     // 8 contraction slots of one column: rows a0 .. +3 and a1 .. +3 of the lane group
     u32x2 lo, hi;
     asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %3\n\ts_waitcnt lgkmcnt(0)" : "=&v"(lo), "=&v"(hi) : "v"(a0), "v"(a1) : "memory");
@@ -1479,7 +1477,7 @@ __device__ __forceinline__ u32x4 tr_frag(unsigned a0, unsigned a1) {     // 8 co
 }
 
 template <typename T, int HD, bool MK>
-__global__ __launch_bounds__(256, MK ? 2 : UF_ATTN_BWD2_WPS) void window_attn_bwd2_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ vt,
+__global__ __launch_bounds__(256, MK ? 2 : ATTN_BWD2_WPS) void window_attn_bwd2_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ vt,
                                                                const float* __restrict__ bias_dense, const float* __restrict__ mask, int n_mask,
                                                                const T* __restrict__ dO, int ldo, T* __restrict__ dq, T* __restrict__ dk,
                                                                T* __restrict__ dvt, T* __restrict__ dqkv, float qscale, float* __restrict__ ws_bias, int n_windows,

@@ -73,58 +73,22 @@ __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + e
 // half-ulp is 7.8e-3): 16x under the storage rounding; the whole Uformer-B output moves by 5.8e-5 (95.9 dB), measured
 // on the oracle, against 2e-3 / 67 dB for bf16 operands themselves.  The f32 (parity) mode never uses it.
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
-#ifndef UF_GELU_POLY
-#define UF_GELU_POLY 0
-#endif
 __device__ __forceinline__ f32x2_t gelu_bf2(f32x2_t x) {
-#if UF_GELU_POLY
-    // FMA-only form: Phi(x) ~ 0.5 + t P(t^2), t = clamp(x, -4, 4), P of degree 6 (weighted minimax fit of (Phi - 0.5) / x for the
-    // error of x Phi): |GELU error| <= 1.9e-4 evaluated in f32 (the sigmoid form: 4.7e-4), and no transcendental -- v_exp / v_rcp
-    // issue at a quarter of the FMA rate and cannot be packed, the 11 instructions here are 2 v_med3 + 9 packed ops per PAIR.
-    const f32x2_t t = f32x2_t{__builtin_amdgcn_fmed3f(x[0], -4.0f, 4.0f), __builtin_amdgcn_fmed3f(x[1], -4.0f, 4.0f)};
-    const f32x2_t u = t * t;
-    f32x2_t q = u * 2.2783789077607253e-08f + (-1.5987216102075763e-06f);
-    q = q * u + 4.79578593512997e-05f;
-    q = q * u + (-0.0008140378049574792f);
-    q = q * u + 0.00877249427139759f;
-    q = q * u + (-0.06457333266735077f);
-    q = q * u + 0.39788350462913513f;
-    return x * (t * q + 0.5f);
-#else
     constexpr float A = -2.3022081985f;    // -2*sqrt(2/pi)*log2(e)
     constexpr float B = -0.10294324f;      // A * 0.044715
     const f32x2_t u = x * (x * x * B + A);
     const f32x2_t d = f32x2_t{__builtin_amdgcn_exp2f(u[0]), __builtin_amdgcn_exp2f(u[1])} + 1.0f;
     return x * f32x2_t{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
-#endif
 }
-// Which GELU the operand type T gets.  bf16: the packed sigmoid form above.  f16: the same form by default -- the whole Uformer-B output
+// Which GELU the operand type T gets.  bf16: the packed sigmoid form above.  f16: the same form -- the whole Uformer-B output
 // moves by 5.8e-5 with it (oracle/bf16_budget.py row "sigmoid-form GELU"), a twentieth of the 1e-3 output tolerance, while an
-// erf-accurate form doubles the VALU work of every activation (two GELUs per hidden channel and token); UF_F16_GELU_ERF=1 builds the
-// f16 kernels with the Abramowitz-Stegun erf form below instead (|GELU error| < 5e-7) for A/B runs.  f32: erff.
-#ifndef UF_F16_GELU_ERF
-#define UF_F16_GELU_ERF 0
-#endif
+// erf-accurate form doubles the VALU work of every activation (two GELUs per hidden channel and token).  f32: erff.
 template <typename T> struct GeluKind { static constexpr int v = 0; };                          // 0: erff (f32 parity mode)
 template <> struct GeluKind<bf16> { static constexpr int v = 1; };                              // 1: packed sigmoid form
-template <> struct GeluKind<f16> { static constexpr int v = UF_F16_GELU_ERF ? 2 : 1; };        // 2: A-S 7.1.26 erf
-// erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7): GELU(x) = max(x, 0) - 0.5 |x| P(t) exp(-z^2), z = |x| / sqrt(2), t = 1 / (1 + p z)
-__device__ __forceinline__ float gelu_as(float x) {
-    const float z = fabsf(x) * 0.70710678118654752440f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
-    float q = fmaf(1.061405429f, t, -1.453152027f);
-    q = fmaf(q, t, 1.421413741f);
-    q = fmaf(q, t, -0.284496736f);
-    q = fmaf(q, t, 0.254829592f) * t;
-    const float e = __builtin_amdgcn_exp2f(z * z * -1.4426950408889634f);
-    return fmaf(-0.70710678118654752440f * z, q * e, fmaxf(x, 0.0f));
-}
+template <> struct GeluKind<f16> { static constexpr int v = 1; };
 // in-place GELU of N (even) values in the flavour the operand type T calls for
 template <typename T, int N> __device__ __forceinline__ void gelu_n(float* v) {
-    if constexpr (GeluKind<T>::v == 2) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) v[i] = gelu_as(v[i]);
-    } else if constexpr (GeluKind<T>::v == 1) {
+    if constexpr (GeluKind<T>::v == 1) {
 #pragma unroll
         for (int i = 0; i < N; i += 2) {
             const f32x2_t g = gelu_bf2(f32x2_t{v[i], v[i + 1]});
@@ -154,11 +118,8 @@ template <typename T> __device__ __forceinline__ float gelu_grad_t(float a) {
 // the input gradient).  2-byte operand types: ONE exp2 / rcp pair serves both (the two separate calls evaluated the same e = 2^u and 1 / (1 + e) twice: 4
 // quarter-rate instructions and 3 multiplies per element more).  dg is gelu_grad_t<T>(a) bit for bit; g is gelu_n's value for every a > -8.4 (below that the
 // clamp of u that keeps dg finite makes g = a 2^-80 instead of a / (1 + 2^u): both are zero to 23 decimal places).  Other types: the two calls.
-#ifndef UF_GELU_PAIR
-#define UF_GELU_PAIR 1      // 0: the two separate evaluations (A/B builds: scripts/build_variant.sh)
-#endif
 template <typename T> __device__ __forceinline__ void gelu_and_grad_t(float a, float& g, float& dg) {
-    if constexpr (GeluKind<T>::v == 1 && UF_GELU_PAIR) {
+    if constexpr (GeluKind<T>::v == 1) {
         constexpr float A = -2.3022081985f, B = -0.10294324f;                 // as gelu_bf2
         const float u = fminf(a * (a * a * B + A), 80.0f);
         const float e = __builtin_amdgcn_exp2f(u);

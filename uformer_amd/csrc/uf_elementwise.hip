@@ -378,7 +378,7 @@ __global__ __launch_bounds__(256) void input_proj_kernel(const float* __restrict
 }
 
 // ---------------------------------------------------------------------------------------
-// a12, second form (round 4): the same convolution with the image tile and the weights staged in LDS.  The first form issues 81 global
+// a12, second form (round 4): the same convolution with the image tile staged in LDS.  The first form issues 81 global
 // loads (54 of them 4-byte broadcast loads) per 432 FMAs and measured 1.1 TB/s of its 134 MB output (123 us at 16 x 256 x 256,
 // profiles/r03_kernels_hip_events.json) -- bound by its own load instructions, not by the store stream.  Here a workgroup owns 4 image
 // rows x TW pixels: the (4 + 2) x (TW + 2) x Cin input halo (zero-padded at the image border) goes to LDS once, coalesced; a thread owns
@@ -387,44 +387,18 @@ __global__ __launch_bounds__(256) void input_proj_kernel(const float* __restrict
 // loads per 432 x 2 packed FMAs instead of 81 loads (54 of them 4-byte broadcasts) per 216.  The E/4 lanes of a pixel still write one contiguous token row.  Same products in the same order as the first form
 // (accumulation starts at the bias, channels outer, rows, then taps): bit-identical results (tests/test_gpu_ops.py).
 // ---------------------------------------------------------------------------------------
-// UF_IP2_DBG, compile-time switches kept from the diagnosis of round 4 (default 130 = 2 | 128): 1 relaxed register bound, 2 weight vectors straight from
-// global memory, 4 zero the unused pad columns, 8 trailing __threadfence, 16 one-dimensional grid, 32 dynamic LDS, 64 a sleep in front of the barrier,
-// 128 EVERY PIXEL VALUE IN A REGISTER OF ITS OWN (the fix), 256 a wait + 32 idle cycles behind the LDS reads.
-//
-// What was wrong.  Under the model's two half-batch streams the first builds of this kernel returned wrong pixels for the side-stream images in 2 of 10 ...
-// 10 of 10 forwards (never alone, never on one stream).  Not a stream-ordering problem: the kernel ALONE on a side stream is wrong whenever a kernel with
-// MFMA waves (the GEMM, leff2, attn_block) runs on the main stream, and exact beside ATen kernels or another stem (scripts/history/r04_dbg8.py,
-// profiles/r04_run17.txt); the wrong elements are columns 48..63 of a 64-pixel tile = lanes 48-63, even channels only, and only the pixels whose products
-// use element 1 of an LDS vector read.  hipcc had compiled `acc[q] += v[q + kx] * wv` into `v_pk_fma_f32 acc, wv, v[2j:2j+1], acc op_sel:[0,1,0]` (the pixel
-// value = the HIGH half of a register pair, selected for both results).  That instruction form returns a wrong LOW result in lanes 48-63 about once in 1e7
-// when an MFMA of another wave is in flight on the SIMD -- reproduced with nothing but that instruction next to a scalar reference
-// (scripts/ubench_hip/pk_opsel.hip, profiles/r04_run19.txt; `v_pk_add_f32 op_sel:[0,1] op_sel_hi:[1,0]` does the same, the src0-select and the
-// op_sel_hi-only broadcast forms measured clean).  Bit 128 moves every pixel value into its own register first, so only the clean `op_sel_hi:[1,0,1]`
-// broadcast form is generated: 0 wrong outputs in 210 co-run launches (profiles/r04_run18.txt), and the idle-cycle variant (256) still fails -- it is the
-// operand select, not the LDS timing.  scripts/check_isa_hazards.py / tests/test_isa_hazards.py keep the hazardous forms out of the whole library.
-#ifndef UF_IP2_DBG
-#define UF_IP2_DBG 130
-#endif
+// Why every pixel value is moved into a register of its own below: hipcc had compiled `acc[q] += v[q + kx] * wv` into `v_pk_fma_f32 ... op_sel:[0,1,0]`,
+// a packed-f32 operand-select form that returns a wrong low result in lanes 48-63 about once in 1e7 when an MFMA of another wave is in flight on the SIMD,
+// so the side-stream images of the model's two half-batch streams came out wrong (tests/test_gpu_model.py:136).  With the moves only the clean
+// `op_sel_hi:[1,0,1]` broadcast form is generated: 0 wrong outputs in 210 co-run launches (profiles/r04_run18.txt).
 __global__ void empty_kernel() {}
 template <int EG>                                   // lanes per pixel = E / 4 (8 for E = 32, 4 for E = 16)
-__global__ __launch_bounds__(256, (UF_IP2_DBG & 1) ? 1 : 4) void input_proj2_kernel(const float* __restrict__ img, const float* __restrict__ w27, const float* __restrict__ bias,
+__global__ __launch_bounds__(256, 4) void input_proj2_kernel(const float* __restrict__ img, const float* __restrict__ w27, const float* __restrict__ bias,
                                                           float* __restrict__ out, int ld_o, int B, int H, int W) {
     constexpr int CIN = 3, E = EG * 4, SL = 8, NSTRIP = 64 / EG, TW = NSTRIP * SL, RS = TW + 4;     // row stride in floats (16-byte multiple; index j = pixel x0 - 1 + j)
-#if (UF_IP2_DBG & 32)
-    extern __shared__ __attribute__((aligned(16))) char dyn_ip2[];
-    float (*Is)[6][RS] = reinterpret_cast<float (*)[6][RS]>(dyn_ip2);
-    float* Ws = reinterpret_cast<float*>(dyn_ip2 + CIN * 6 * RS * 4);
-#else
     __shared__ __attribute__((aligned(16))) float Is[CIN][6][RS];
-    __shared__ __attribute__((aligned(16))) float Ws[27 * E];
-#endif
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    if (UF_IP2_DBG & 16) {                              // 1-D launch: x = tile column fastest, then tile row, then image
-        const int tx_n = (W + TW - 1) / TW, ty_n = (H + 3) / 4;
-        bx = (int)blockIdx.x % tx_n; by = ((int)blockIdx.x / tx_n) % ty_n; bz = (int)blockIdx.x / (tx_n * ty_n);
-    }
-    const int x0 = bx * TW, y0 = by * 4, b = bz;
+    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * 4, b = blockIdx.z;
     for (int i = tid; i < CIN * 6 * (TW + 2); i += 256) {
         const int j = i % (TW + 2), r = (i / (TW + 2)) % 6, ci = i / ((TW + 2) * 6);
         const int ix = x0 - 1 + j, iy = y0 - 1 + r;
@@ -432,9 +406,6 @@ __global__ __launch_bounds__(256, (UF_IP2_DBG & 1) ? 1 : 4) void input_proj2_ker
         const float v = img[(size_t)((b * CIN + ci) * H + (ok ? iy : 0)) * W + (ok ? ix : 0)];
         Is[ci][r][j] = ok ? v : 0.0f;
     }
-    if (!(UF_IP2_DBG & 2)) { for (int i = tid; i < 27 * E; i += 256) Ws[i] = w27[i]; }
-    if (UF_IP2_DBG & 4) { for (int i = tid; i < CIN * 6 * RS; i += 256) if (i % RS >= TW + 2) (&Is[0][0][0])[i] = 0.f; }
-    if (UF_IP2_DBG & 64) { __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127); }
     __syncthreads();
     const int e = (lane % EG) * 4, strip = lane / EG;
     const int yh = y0 + wave, xs = x0 + strip * SL;
@@ -451,14 +422,11 @@ __global__ __launch_bounds__(256, (UF_IP2_DBG & 1) ? 1 : 4) void input_proj2_ker
             const f32x4 a0 = *reinterpret_cast<const f32x4*>(row), a1 = *reinterpret_cast<const f32x4*>(row + 4);
             const f32x2_t a2 = *reinterpret_cast<const f32x2_t*>(row + 8);
             float v[SL + 2] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3], a2[0], a2[1]};
-            if (UF_IP2_DBG & 256) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory");       // diagnosis: a long gap between the LDS reads and their first use
-            if (UF_IP2_DBG & 128) {                                                                                  // diagnosis / fix: every pixel value in a register of its own
 #pragma unroll
-                for (int k = 0; k < SL + 2; ++k) asm volatile("v_mov_b32 %0, %1" : "=v"(v[k]) : "v"(v[k]));
-            }
+            for (int k = 0; k < SL + 2; ++k) asm volatile("v_mov_b32 %0, %1" : "=v"(v[k]) : "v"(v[k]));       // every pixel value in a register of its own
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) {
-                const f32x4 wv = (UF_IP2_DBG & 2) ? *reinterpret_cast<const f32x4*>(w27 + (ci * 9 + ky * 3 + kx) * E + e) : *reinterpret_cast<const f32x4*>(&Ws[(ci * 9 + ky * 3 + kx) * E + e]);
+                const f32x4 wv = *reinterpret_cast<const f32x4*>(w27 + (ci * 9 + ky * 3 + kx) * E + e);
 #pragma unroll
                 for (int q = 0; q < SL; ++q) acc[q] += v[q + kx] * wv;
             }
@@ -472,7 +440,6 @@ __global__ __launch_bounds__(256, (UF_IP2_DBG & 1) ? 1 : 4) void input_proj2_ker
         for (int i = 0; i < 4; ++i) a[i] = a[i] >= 0.f ? a[i] : 0.01f * a[i];
         *reinterpret_cast<f32x4*>(out + (size_t)((b * H + yh) * W + xs + q) * ld_o + e) = a;
     }
-    if (UF_IP2_DBG & 8) __threadfence();
 }
 
 // ---------------------------------------------------------------------------------------
@@ -860,11 +827,9 @@ extern "C" int uf_input_proj_fwd(const float* img, const float* w27, const float
     // packed-f32 operand-select hazard that corrupted it beside MFMA kernels was found and removed (see the kernel comment); UF_VARIANT="stem=1": first form.
     const bool v1 = variant("stem", 2) == 1;
     if (!v1 && Cin == 3 && (E == 32 || E == 16) && (H + 3) / 4 <= 65535) {
-        const dim3 g32 = (UF_IP2_DBG & 16) ? dim3(((W + 63) / 64) * ((H + 3) / 4) * B) : dim3((W + 63) / 64, (H + 3) / 4, B);
-        const dim3 g16 = (UF_IP2_DBG & 16) ? dim3(((W + 127) / 128) * ((H + 3) / 4) * B) : dim3((W + 127) / 128, (H + 3) / 4, B);
-        const int dyn = (UF_IP2_DBG & 32) ? 16384 : 0;
-        if (E == 32) hipLaunchKernelGGL(input_proj2_kernel<8>, g32, dim3(256), dyn, (hipStream_t)stream, img, w27, bias, out, ld_o, B, H, W);
-        else hipLaunchKernelGGL(input_proj2_kernel<4>, g16, dim3(256), dyn, (hipStream_t)stream, img, w27, bias, out, ld_o, B, H, W);
+        const dim3 g32((W + 63) / 64, (H + 3) / 4, B), g16((W + 127) / 128, (H + 3) / 4, B);
+        if (E == 32) hipLaunchKernelGGL(input_proj2_kernel<8>, g32, dim3(256), 0, (hipStream_t)stream, img, w27, bias, out, ld_o, B, H, W);
+        else hipLaunchKernelGGL(input_proj2_kernel<4>, g16, dim3(256), 0, (hipStream_t)stream, img, w27, bias, out, ld_o, B, H, W);
         return check_launch("input_proj");
     }
     if (px == 8) hipLaunchKernelGGL(input_proj_kernel<8>, dim3((nx + 255) / 256, H, B), dim3(256), 0, (hipStream_t)stream, img, w27, bias, out, ld_o, B, Cin, H, W, E);

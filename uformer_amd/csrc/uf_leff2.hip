@@ -32,28 +32,18 @@ struct Leff2Params {
 
 constexpr int KCW = 64;  // hidden channels one producer group (4 waves) convolves per interval
 
-// UF_MCONV: how the producers of the 2-byte operand types evaluate the depthwise 3x3 (round 4).
-//   0  VALU stencil (rounds 1-3): 9 FMAs per output + one bf16->f32 unpack per (output, column tap) -- 298 VALU instructions per producer
+// How the producers evaluate the depthwise 3x3 (round 4).
+//   f32 (parity mode): VALU stencil (rounds 1-3): 9 FMAs per output + one unpack per (output, column tap) -- 298 VALU instructions per producer
 //      wave and interval; the PMC passes of round 3 show the VALU pipe of a SIMD (one wave-instruction per 4 cycles) as the busiest
 //      resource of this kernel (47-55 % at every width), the MFMA pipe at 5-19 %.
-//   1  MFMA stencil, taps rounded to the operand type: a 16-channel group of a 16-pixel tile is D[c][p] = sum_k A[c][k] B[k][p] with
+//   2-byte operand types: MFMA stencil, taps rounded to the operand type: a 16-channel group of a 16-pixel tile is D[c][p] = sum_k A[c][k] B[k][p] with
 //      k = (tap, c'), A[c][(tap, c')] = w[tap][c] delta(c, c') (a block-diagonal weight operand built in registers: one non-zero 16-bit
 //      slot per lane) and B[(tap, c')][p] = halo[p + tap][c'] = a 16-byte ds_read_b128 of the DMA-staged halo tile AS IT LIES in LDS --
 //      no unpack, no FMA on the VALU; 15/16 of the MFMA's multiplies are zeros, on a pipe that is idle.  K = 9 taps x 16 = 5 k-steps
 //      of 32 (two taps per step).  The accumulator starts at the conv bias, GELU runs on the accumulator registers, and the result is
 //      written to the operand tile of linear2 exactly as before.
-//   2  the same with every tap split into hi + lo parts of the operand type (9 k-steps: slots = {hi, lo} x 16 channels): products of
-//      2-byte operands are exact in the f32 accumulator, so the taps count with 16 (bf16) / 22 (f16) mantissa bits -- the f32 taps of
-//      the VALU form to 2^-17; only the summation order differs.
-// Measured (profiles/r04_run1.txt, same box, two interleaved runs): leff2 per step 2.948 ms (0) / 2.652 (1) / 3.097 (2); Uformer-B f16 error vs the
-// oracle 2.95e-4 / 2.72e-4 / 2.72e-4, bf16 1.89e-3 / 2.06e-3 / 1.92e-3.  Default 1: the split form's four extra k-steps and its per-tap
-// hi / lo arithmetic cost more issue slots than the VALU stencil it replaces.
-#ifndef UF_MCONV
-#define UF_MCONV 1
-#endif
-#ifndef UF_LEFF2_CP_DEFAULT
-#define UF_LEFF2_CP_DEFAULT false
-#endif
+// Measured (profiles/r04_run1.txt, same box, two interleaved runs): leff2 per step 2.948 ms (VALU) / 2.652 (MFMA) / 3.097 (MFMA with every tap split
+// into hi + lo parts, nine k-steps); Uformer-B f16 error vs the oracle 2.95e-4 / 2.72e-4 / 2.72e-4, bf16 1.89e-3 / 2.06e-3 / 1.92e-3.
 template <typename T> __device__ __forceinline__ void cvt8(const char* p, float* f);
 template <> __device__ __forceinline__ void cvt8<bf16>(const char* p, float* f) { unpack8<bf16>(*reinterpret_cast<const u32x4*>(p), f); }
 template <> __device__ __forceinline__ void cvt8<f16>(const char* p, float* f) { unpack8<f16>(*reinterpret_cast<const u32x4*>(p), f); }
@@ -82,7 +72,7 @@ __device__ __forceinline__ void put8(float* p, const float* f) {
 template <typename T, int C, int NPG, int NC, int NBUF, int WPS, int PW = 4, int CP = 0>
 __global__ __launch_bounds__((PW * NPG + NC) * 64, WPS) void leff2_kernel(const Leff2Params p) {
     constexpr int NP = PW * NPG;                  // producer waves: PW (4 or 8) per 64-channel group of the interval
-    constexpr int MC = sizeof(T) == 2 ? UF_MCONV : 0;   // depthwise 3x3 on the MFMA (2-byte operand types), see UF_MCONV
+    constexpr int MC = sizeof(T) == 2 ? 1 : 0;   // 1: depthwise 3x3 on the MFMA (2-byte operand types), 0: on the VALU, see above
     static_assert(PW == 4 || (PW == 8 && MC != 0), "8 producer waves per group: MFMA stencil only (two pixel tiles per wave)");
     static_assert(CP == 0 || (MC != 0 && PW == 4 && NPG == 1 && NC == 4 * CP), "consumer stencil jobs: MFMA stencil, 4 producers, one job per consumer wave");
     constexpr int PTW = 16 / PW - CP;             // pixel tiles (16 pixels) per producer wave
@@ -145,10 +135,10 @@ __global__ __launch_bounds__((PW * NPG + NC) * 64, WPS) void leff2_kernel(const 
 #pragma unroll
     for (int d = 0; d < 4; ++d) msk[d] = ((fg & 1) == (fr >> 3) && d == ((fr & 7) >> 1)) ? 0xffffffffu : 0u;
     const int gq = (producer ? wave : wave - NP) & 3;
-    int boff[MC == 2 ? 9 : 5];
+    int boff[5];
 #pragma unroll
-    for (int ks = 0; ks < (MC == 2 ? 9 : 5); ++ks) {
-        int tap = MC == 2 ? ks : 2 * ks + (fg >> 1);
+    for (int ks = 0; ks < 5; ++ks) {
+        int tap = 2 * ks + (fg >> 1);
         tap = tap < 9 ? tap : 8;
         const int hy = (fr >> 3) + tap / 3, hx = (fr & 7) + tap % 3;
         boff[ks] = ((hy * HW_ + hx) * 8 + ((gq * 2 + (fg & 1)) ^ (hx & 6))) * 16;
@@ -226,7 +216,7 @@ __global__ __launch_bounds__((PW * NPG + NC) * 64, WPS) void leff2_kernel(const 
                 char* At = At0 + (i & 1) * AT_BYTES + grp * KCW * SZ;
                 if constexpr (MC != 0) {
                     // ---- depthwise 3x3 on the MFMA: this wave = the 16-channel group gq of its 64-channel halo tile, pixel tiles pt0 .. pt0 + PTW - 1 ----
-                    mconv_job<T, MC, PTW, KC, SAT, 2 * HW_ * PS>(Hs, Wl, At, gq, pt0, boff, msk, hshift, fr, fg);
+                    mconv_job<T, PTW, KC, SAT, 2 * HW_ * PS>(Hs, Wl, At, gq, pt0, boff, msk, hshift, fr, fg);
                 } else {
                 float o[SR][8];
 #pragma unroll
@@ -375,7 +365,7 @@ __global__ __launch_bounds__((PW * NPG + NC) * 64, WPS) void leff2_kernel(const 
             if (j < NTOT) {       // this wave's stencil job of interval j: group gq, pixel tile 4 - CP + cw / 4 (halo tile landed before the last barrier)
                 const char* Hs = Ring + (j % NBUF) * BUFB;
                 const float* Wl = reinterpret_cast<const float*>(Ring + (j % NBUF) * BUFB + NPG * HGB);
-                mconv_job<T, MC, 1, KC, SAT, 2 * HW_ * PS>(Hs, Wl, At0 + (j & 1) * AT_BYTES, gq, 4 - CP + (cw >> 2), boff, msk, hshift, fr, fg);
+                mconv_job<T, 1, KC, SAT, 2 * HW_ * PS>(Hs, Wl, At0 + (j & 1) * AT_BYTES, gq, 4 - CP + (cw >> 2), boff, msk, hshift, fr, fg);
             }
         }
         ct1 = __builtin_readcyclecounter(); ctw += ct1 - ct0; ct0 = ct1;
@@ -430,28 +420,17 @@ int launch_v(const Leff2Params& p, hipStream_t st) {
 // Shape -> variant.  bf16: C <= 128: 8-wave workgroups small enough (51 KiB, <= 80 registers) for three per CU; C = 256: two per
 // CU (3-deep DMA ring, 128 registers); C = 512: 4 stencil + 8 MFMA waves, one workgroup per CU (the consumers' accumulators and
 // their W2 prefetch need 168 registers).  f32 (parity mode): one configuration per width.
-// depth of the halo-tile DMA ring (NBUF) per width (compile-time knobs of the round-5 experiment).  Hypothesis: a workgroup has NBUF - 1 slots in
+// depth of the halo-tile DMA ring (NBUF) per width (round-5 experiment).  Hypothesis: a workgroup has NBUF - 1 slots in
 // flight while it convolves one, so an interval cannot be shorter than (loaded HBM latency) / (NBUF - 1) -- C = 512 with 3 slots: 63 us / 32 intervals
 // = 2 us.  Measured (profiles/r05_run8_ring.txt): C = 512 with 3 / 5 / 8 slots 66.2 / 66.3 / 67.0 us, C = 256 (enc3 form) 3 / 6 slots 30.3 / 31.5,
 // dec1 on one 16-wave workgroup per CU with 5 / 8 slots 100.9 / 96.2 against 83.3 for two 8-wave workgroups with 3: the ring is NOT the limit;
 // the role stamps (profiles/r05_run9_leff2_stamps.txt) show the consumers' interval (2.2 K cycles of work for 0.5 K of MFMA at C = 512) as the
 // longer chain.
-#ifndef UF_NB512
-#define UF_NB512 3
-#endif
-#ifndef UF_NB256
-#define UF_NB256 3
-#endif
-#ifndef UF_NB256E
-#define UF_NB256E 3
-#endif
-#ifndef UF_L256_BIG
-#define UF_L256_BIG 0   // 1: dec1-sized grids on 8 + 8 waves, one workgroup per CU, NBUF = UF_NB256E
-#endif
+constexpr int NB512 = 3, NB256 = 3, NB256E = 3;   // C = 512, C = 256, C = 256 on 8 + 8 waves (enc3 form)
 template <typename T, int C>
 int launch_c(const Leff2Params& p, hipStream_t st) {
     const int tiles = p.B * (p.H / 8) * (p.W / 8);
-    if constexpr (sizeof(T) == 2 && UF_MCONV != 0 && C >= 32) {
+    if constexpr (sizeof(T) == 2 && C >= 32) {
         // 8 producer waves per 64-channel group (two pixel tiles each) where the grid is at most one round of workgroups: a producer wave
         // is a serial chain of LDS round trips (taps -> fragments -> halo reads -> MFMA -> GELU -> operand tile: ~2 K cycles per interval
         // for ~250 instructions, scripts/ubench.py stamps2), so with nothing else resident on the CU shorter chains win -- enc2 (C = 128,
@@ -461,14 +440,14 @@ int launch_c(const Leff2Params& p, hipStream_t st) {
         const bool force = ev == 1, never = ev == 2;
         // (Stencil jobs on the consumer waves -- template parameter CP -- measured -8 % in round 4, profiles/r04_run7.txt, and are not instantiated.)
         if constexpr (C == 128) { if (!never && (force || tiles <= 1024)) return launch_v<T, C, 1, 4, 2, 6, 8>(p, st); }
-        else if constexpr (C == 256) { if (!never && (force || tiles <= 256 || UF_L256_BIG)) return launch_v<T, C, 1, 8, UF_NB256E, 4, 8>(p, st); }
+        else if constexpr (C == 256) { if (!never && (force || tiles <= 256)) return launch_v<T, C, 1, 8, NB256E, 4, 8>(p, st); }
         else if constexpr (C == 512) { if (force) return launch_v<T, C, 1, 8, 4, 4, 8>(p, st); }
         else { if (force) return launch_v<T, C, 1, 4, 2, 6, 8>(p, st); }
     }
     if constexpr (sizeof(T) == 2) {
         if constexpr (C <= 128) return launch_v<T, C, 1, 4, 2, 6>(p, st);
-        else if constexpr (C == 256) return launch_v<T, C, 1, 4, UF_NB256, 4>(p, st);
-        else return launch_v<T, C, 1, 8, UF_NB512, 3>(p, st);
+        else if constexpr (C == 256) return launch_v<T, C, 1, 4, NB256, 4>(p, st);
+        else return launch_v<T, C, 1, 8, NB512, 3>(p, st);
     } else {
         (void)tiles;
         if constexpr (C <= 256) return launch_v<T, C, 1, 4, 2, 2>(p, st);

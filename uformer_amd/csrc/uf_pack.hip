@@ -48,7 +48,7 @@ struct SmallPack {
 };
 
 // The depthwise taps are ROUNDED TO THE OPERAND TYPE here (round 6): the fused inference kernel evaluates the stencil on the matrix pipe with
-// taps of the operand type (uf_leff2.hip, UF_MCONV = 1) while the op-level training kernels took the f32 taps -- eval and train forwards of the same weights
+// taps of the operand type (uf_leff2.hip) while the op-level training kernels took the f32 taps -- eval and train forwards of the same weights
 // differed in tap precision, and in the recompute form the loss came from one function and its gradient from another.  With the pack rounding them, every
 // training kernel (forward stencil, input gradient with the flipped taps) and the fused forward see the same values; the tap GRADIENT stays f32 (straight through).
 template <typename T> __device__ __forceinline__ float round_tap(float w) {
