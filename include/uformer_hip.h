@@ -539,6 +539,30 @@ int uf_crop_augment(const void* src, int src_is_u8, int src_hwc, float* out, con
 /* MixUp_AUG.aug (utils/dataset_utils.py:37-53): out[b] = lam[b] x[b] + (1 - lam[b]) x[perm[b]]; out must not alias x. */
 int uf_mixup(const float* x, float* out, const float* lam, const int* perm, int B, long long per_sample, void* stream);
 
+/* ---- cross-modulator attention of a decoder block (LeWinTransformerBlock(cross_modulator=True), model.py:873-877, :945-949; Attention :549-595;
+ * LinearProjection.forward with attn_kv :431-442), one kernel, in place on the f32 stream:
+ *   x[m] += proj( softmax_over_64_keys( q[m]_h K_h^T ) V_h ),   q[m] = (x[m] Wq^T + bq) hd^-0.5,   K | V = to_kv(cross_modulator.weight)
+ * for every row m on its own: the 64 learned key / value tokens are the same for every row, there is no window geometry, no relative-position
+ * bias and no mask, and no LayerNorm -- the reference computes norm_cross(x) and overwrites the result on the next line (model.py:946-947), so
+ * the query is the UN-normalised stream.  The caller projects K and V once per parameter version (64 rows: parameter-only glue).
+ * Rounding points (those of uf_window_attention_fwd and uf_linear_residual_fwd): the x rows are rounded to T as a GEMM operand; q accumulates in
+ * f32, gets the f32 bias, then the scale, and is rounded to T; the scores and the softmax are f32 (2-byte types: exp2 of the scores times log2(e));
+ * e = exp(s - max) is rounded to T as the operand of e V; o = (e V) / sum(e) (the f32 sum of the unrounded e) is rounded to T; the projection
+ * accumulates in f32, the bias and the residual are added in f32 and the stream is not rounded.
+ * One workgroup per 64 consecutive rows (32 for f32 at C = 512): M a positive multiple of 64.  C in {16,32,64,128,256,512}; hd = C / heads in
+ * {16, 32}; x and every operand 16-byte aligned, ld >= C and ld % 4 == 0; columns [C, ld) of x are not touched.  No workspace. */
+typedef struct uf_cross_params {
+    const void*  wq_fm;   /* T (C,C) cross_attn.qkv.to_q.weight, fragment-major (uf_pack_weight_fm) */
+    const float* bq;      /* f32 (C) */
+    const void*  k;       /* T [heads][64][hd]   = T( to_kv(cross_modulator.weight) ) k half, NOT scaled */
+    const void*  vt;      /* T [heads][hd][64]   v half, transposed as uf_qkv_fwd's vt */
+    const void*  wp_fm;   /* T (C,C) cross_attn.proj.weight, fragment-major */
+    const float* bp;      /* f32 (C) */
+    int32_t heads;
+} uf_cross_params;
+int uf_cross_attn_fwd(const uf_cross_params* p, float* x /* f32 [M][ld], in place */, int ld, int M, int C,
+                      uf_dtype dtype, void* stream);
+
 /* ---- a9 (boundary): Uformer.forward (model.py:1269-1305) ------------------------------------ */
 typedef struct uf_model_desc {
     int32_t embed_dim, dd_in, in_chans;
@@ -553,6 +577,9 @@ typedef struct uf_model_desc {
     const void* up_w[4];   /* upsample_i.deconv.0.weight repacked T[4Cout][Cin] */
     const float* up_b[4];
     const void* down_w_fm[4]; /* (round 6, appended) down_w in the fragment-major layout of uf_pack_weight_fm(down_w, ., 2C, 16C), or NULL: see uf_downsample_fm_fwd */
+    const uf_cross_params* cross; /* (appended) NULL, or sum(depths) entries aligned with `blocks`; an entry with wq_fm == NULL: the block has no cross-modulator.
+                                     uf_uformer_fwd runs uf_cross_attn_fwd on the block's rows before its attention half (model.py:945-949; the reference sets
+                                     the flag on decoderlayer_0..3 only, :1196-1245).  uf_uformer_win4_fwd does not read it. */
 } uf_model_desc;
 
 size_t uf_uformer_workspace_bytes(const uf_model_desc* d, int B, int H, int W, uf_dtype dtype);

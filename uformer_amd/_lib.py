@@ -53,6 +53,11 @@ class Block4Params(C.Structure):
         ("heads", C.c_int32)]
 
 
+class CrossParams(C.Structure):
+    """``uf_cross_params`` (include/uformer_hip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("wq_fm", "bq", "k", "vt", "wp_fm", "bp")] + [("heads", C.c_int32)]
+
+
 class ModelDesc(C.Structure):
     """``uf_model_desc`` (include/uformer_hip.h)."""
     _fields_ = [
@@ -63,6 +68,7 @@ class ModelDesc(C.Structure):
         ("down_w", C.c_void_p * 4), ("down_b", C.c_void_p * 4),
         ("up_w", C.c_void_p * 4), ("up_b", C.c_void_p * 4),
         ("down_w_fm", C.c_void_p * 4),
+        ("cross", C.POINTER(CrossParams)),
     ]
 
 
@@ -127,6 +133,7 @@ SIGNATURES = {
     "uf_lewin_attn_fwd": (I, [C.POINTER(BlockParams), P, I, I, I, I, I, P, I, I, P, c_size_t, P]),
     "uf_leff_fwd": (I, [C.POINTER(BlockParams), P, I, I, I, I, I, I, P, c_size_t, P]),
     "uf_ffn_fwd": (I, [P, I, P, P, P, P, P, P, P, I, I, I, I, P]),
+    "uf_cross_attn_fwd": (I, [C.POINTER(CrossParams), P, I, I, I, I, P]),
     "uf_mlp_fwd": (I, [C.POINTER(BlockParams), P, I, I, I, I, I, I, P, c_size_t, P]),
     "uf_lewin_attn_train_fwd": (I, [C.POINTER(BlockParams), P, I, P, I, I, I, I, I, P, I, P, P, P, P, P, P, P, P]),
     "uf_lewin_block_fwd": (I, [C.POINTER(BlockParams), P, I, I, I, I, I, P, I, I, P, c_size_t, P]),

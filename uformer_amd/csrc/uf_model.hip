@@ -396,7 +396,13 @@ int forward_one_stream(const uf_model_desc* d, const uf_block4_params* bneck, co
     // in round 3 -- profiles/r03_chunk_ab.txt -- and is gone.)
     auto run_stage = [&](int s, float* x, int ld) -> int {
         for (int i = 0; i < d->depths[s]; ++i, ++blk) {
-            int r = (s == 4 && bneck) ? uf_lewin_block4_fwd(bneck + i, x, ld, B, pl.res_h[s], pl.res_w[s], pl.C[s], nullptr, nullptr, dtype, bws, pl.blk_bytes, st)
+            // cross-modulator attention in front of the block (model.py:945-949): row-local, on the block's own stream rows
+            const uf_cross_params* cr = (d->cross && !bneck) ? d->cross + (blk - d->blocks) : nullptr;
+            if (cr && cr->wq_fm) {
+                int r = uf_cross_attn_fwd(cr, x, ld, (int)pl.M[s], pl.C[s], dtype, st);
+                if (r) return r;
+            }
+            int r =(s == 4 && bneck) ? uf_lewin_block4_fwd(bneck + i, x, ld, B, pl.res_h[s], pl.res_w[s], pl.C[s], nullptr, nullptr, dtype, bws, pl.blk_bytes, st)
                                       : uf_lewin_block_fwd(blk, x, ld, B, pl.res_h[s], pl.res_w[s], pl.C[s], nullptr, 0, dtype, bws, pl.blk_bytes, st);
             if (r) return r;
         }

@@ -198,6 +198,40 @@ class WindowAttention(nn.Module):
         return flops
 
 
+CROSS_MODULATOR_WIDTHS = (16, 32, 64, 128, 256, 512)      # uf_cross_attn_fwd
+
+
+class Attention(nn.Module):
+    """model.py:549-621: the ``cross_attn`` of a block built with ``cross_modulator=True``.  Holds the parameters (a LinearProjection whatever
+    ``token_projection`` says, model.py:558, and ``proj``; no relative-position table); inside a LeWinTransformerBlock it runs as one
+    ``uf_cross_attn_fwd`` launch against the block's 64 ``cross_modulator`` tokens."""
+
+    def __init__(self, dim, num_heads, token_projection='linear', qkv_bias=True, qk_scale=None, attn_drop=0., proj_drop=0.):
+        super().__init__()
+        if qk_scale is not None or attn_drop or proj_drop:
+            raise NotImplementedError("qk_scale / attention dropout are never set by the reference archs")
+        if dim not in CROSS_MODULATOR_WIDTHS or dim % num_heads or dim // num_heads not in (16, 32):
+            raise NotImplementedError(f"cross_modulator is built for blocks of width 16 ... 512 with head_dim 16 or 32 (uf_cross_attn_fwd); this block "
+                                      f"has width {dim} and {num_heads} heads (embed_dim 64 gives head_dim 64)")
+        self.dim = dim
+        self.num_heads = num_heads
+        self.scale = (dim // num_heads) ** -0.5
+        self.qkv = LinearProjection(dim, num_heads, dim // num_heads, bias=qkv_bias)
+        self.token_projection = token_projection
+        self.proj = nn.Linear(dim, dim)
+
+    def forward(self, x, attn_kv=None, mask=None):
+        raise NotImplementedError("cross_modulator: the cross attention runs fused inside its block (uf_cross_attn_fwd); call the "
+                                  "LeWinTransformerBlock, there is no stand-alone Attention forward")
+
+    def extra_repr(self) -> str:
+        return f'dim={self.dim}, num_heads={self.num_heads}'
+
+    def flops(self, q_num, kv_num):
+        """model.py:600-618 (without its print)."""
+        return self.qkv.flops(q_num, kv_num) + 2 * self.num_heads * q_num * (self.dim // self.num_heads) * kv_num + q_num * self.dim * self.dim
+
+
 class LeFF(nn.Module):
     """model.py:654-699."""
 
@@ -340,14 +374,13 @@ class OutputProj(nn.Module):
 
 class LeWinTransformerBlock(nn.Module):
     """model.py:850-1008 (``token_mlp`` 'leff', or 'ffn' / 'mlp' for the reference's Mlp; ``token_projection`` 'linear', or 'conv' for the
-    reference's ConvProjection, inference only; no cross-modulator)."""
+    reference's ConvProjection, inference only; ``cross_modulator=True`` adds the
+    reference's ``cross_modulator`` / ``cross_attn`` / ``norm_cross``, inference only)."""
 
     def __init__(self, dim, input_resolution, num_heads, win_size=8, shift_size=0, mlp_ratio=4., qkv_bias=True,
                  qk_scale=None, drop=0., attn_drop=0., drop_path=0., act_layer=nn.GELU, norm_layer=nn.LayerNorm,
                  token_projection='linear', token_mlp='leff', modulator=False, cross_modulator=False):
         super().__init__()
-        if cross_modulator:
-            raise NotImplementedError("cross_modulator is never enabled by get_arch (SURVEY.md section 2 row 10)")
         if token_mlp not in ('leff', 'ffn', 'mlp'):
             raise NotImplementedError(f"token_mlp={token_mlp!r}: 'leff' and 'ffn' / 'mlp' are built ('fastleff' needs a third-party CUDA package, "
                                       "model.py:895-896)")
@@ -373,7 +406,15 @@ class LeWinTransformerBlock(nn.Module):
             raise NotImplementedError("a 4x4-window block with a modulator: the reference's (64, C) embedding (model.py:868-869) does not broadcast "
                                       "onto 16-token windows (model.py:967-969)")
         self.modulator = nn.Embedding(win_size * win_size, dim) if modulator else None
-        self.cross_modulator = None
+        if cross_modulator:                     # model.py:873-877, registered between modulator and norm1
+            if self.win_size != 8:
+                raise NotImplementedError("cross_modulator is built for 8x8-window blocks (img_size 64 clamps the bottleneck's window to 4)")
+            self.cross_modulator = nn.Embedding(win_size * win_size, dim)
+            self.cross_attn = Attention(dim, num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale, attn_drop=attn_drop, proj_drop=drop,
+                                        token_projection=token_projection)
+            self.norm_cross = norm_layer(dim)   # in the state_dict, never read: the reference overwrites its output (model.py:947-948)
+        else:
+            self.cross_modulator = None
         self.norm1 = norm_layer(dim)
         self.attn = WindowAttention(dim, win_size=(self.win_size, self.win_size), num_heads=num_heads, qkv_bias=qkv_bias,
                                     qk_scale=qk_scale, attn_drop=attn_drop, proj_drop=drop, token_projection=token_projection)
@@ -387,6 +428,7 @@ class LeWinTransformerBlock(nn.Module):
                                           f"width {dim} and window {self.win_size} (img_size 64 and embed_dim 64 take token_mlp='leff' only)")
             self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
         self._packed = None
+        self._packed_cross = None
 
     def extra_repr(self) -> str:
         return (f"dim={self.dim}, input_resolution={self.input_resolution}, num_heads={self.num_heads}, "
@@ -402,6 +444,15 @@ class LeWinTransformerBlock(nn.Module):
                 bp, keep = packing.pack_block(sd, "", self.num_heads, self.shift_size, dtype)
             self._packed = (key, bp, keep)
         return self._packed[1]
+
+    def _pack_cross(self, dtype):
+        """The ``uf_cross_params`` of this block's cross-modulator, cached by (data_ptr, _version) of the parameters it is made of."""
+        sd = {k: v for k, v in self.state_dict(keep_vars=True).items() if k.startswith(("cross_modulator.", "cross_attn."))}
+        key = (dtype, tuple((v.data_ptr(), v._version) for v in sd.values()))
+        if self._packed_cross is None or self._packed_cross[0] != key:
+            cp, keep = packing.pack_cross(sd, "", self.num_heads, dtype)
+            self._packed_cross = (key, cp, keep)
+        return self._packed_cross[1]
 
     def user_attn_mask(self, mask: Tensor, H: int, W: int) -> Tensor:
         """Dense additive mask (B*nW,64,64) from the user ``mask`` argument, model.py:914-921
@@ -420,6 +471,8 @@ class LeWinTransformerBlock(nn.Module):
             from . import train
             if self.token_projection == 'conv':
                 raise NotImplementedError(train.TOKEN_PROJECTION_TRAINING)
+            if self.cross_modulator is not None:
+                raise NotImplementedError(train.CROSS_MODULATOR_TRAINING)
             if not x.is_cuda:
                 raise UformerHipError("LeWinTransformerBlock runs on the GPU only; there is no CPU path")
             named = [(n, t) for n, t in self.state_dict(keep_vars=True).items()]
@@ -456,6 +509,9 @@ class LeWinTransformerBlock(nn.Module):
             nbytes = lib.uf_block_workspace_bytes(B * L, Cc, dt)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
             bp = self._pack(compute_dtype)
+            if self.cross_modulator is not None:    # model.py:945-949, on the un-normalised stream, before the attention half
+                _lib.check(lib.uf_cross_attn_fwd(self._pack_cross(compute_dtype), y.data_ptr(), Cc, B * L, Cc, dt,
+                                                 torch.cuda.current_stream().cuda_stream), "uf_cross_attn_fwd")
             _lib.check(lib.uf_lewin_block_fwd(bp, y.data_ptr(), Cc, B, H, W, Cc, None if um is None else um.data_ptr(),
                                               0 if um is None else um.shape[0], dt, ws.data_ptr(), nbytes,
                                               torch.cuda.current_stream().cuda_stream), "uf_lewin_block_fwd")
@@ -472,6 +528,9 @@ class BasicUformerLayer(nn.Module):
         if use_checkpoint and token_projection == 'conv':
             from .train import TOKEN_PROJECTION_TRAINING
             raise NotImplementedError("use_checkpoint: " + TOKEN_PROJECTION_TRAINING)
+        if use_checkpoint and cross_modulator:
+            from .train import CROSS_MODULATOR_TRAINING
+            raise NotImplementedError("use_checkpoint: " + CROSS_MODULATOR_TRAINING)
         self.dim = dim
         self.input_resolution = input_resolution
         self.depth = depth
@@ -519,7 +578,8 @@ class Uformer(nn.Module):
         self.compute_dtype = compute_dtype
         self.cfg = UformerConfig(img_size=img_size, in_chans=in_chans, dd_in=dd_in, embed_dim=embed_dim,
                                  depths=tuple(depths), num_heads=tuple(num_heads), win_size=win_size, mlp_ratio=mlp_ratio,
-                                 modulator=modulator, shift_flag=shift_flag, token_mlp=token_mlp, token_projection=token_projection)
+                                 modulator=modulator, shift_flag=shift_flag, token_mlp=token_mlp, token_projection=token_projection,
+                                 cross_modulator=bool(cross_modulator))
         bad = self.cfg.unsupported_clamp() if win_size == 8 else None
         if bad is not None:       # model.py:863-866 clamps a stage's window to its resolution; built: 8, and 4 for the bottleneck alone
             s_, res_, win_ = bad
@@ -530,15 +590,21 @@ class Uformer(nn.Module):
         conv_dpr = [drop_path_rate] * depths[4]
         dec_dpr = enc_dpr[::-1]
 
+        if cross_modulator and self.cfg.stage_windows()[4] != 8:
+            raise NotImplementedError(f"cross_modulator is built for models whose every stage runs on 8x8 windows; img_size={img_size} gives the "
+                                      f"bottleneck 4x4 windows (uf_uformer_win4_fwd does not run the cross attention)")
+        if cross_modulator and use_checkpoint:
+            from .train import CROSS_MODULATOR_TRAINING
+            raise NotImplementedError("use_checkpoint: " + CROSS_MODULATOR_TRAINING)
+
         def layer(s, dim, res, dpr, mod):
             return BasicUformerLayer(dim=dim, output_dim=dim, input_resolution=(res, res), depth=depths[s],
                                      num_heads=num_heads[s], win_size=win_size, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias,
                                      qk_scale=qk_scale, drop=drop_rate, attn_drop=attn_drop_rate, drop_path=dpr,
                                      norm_layer=norm_layer, use_checkpoint=use_checkpoint, token_projection=token_projection,
-                                     token_mlp=token_mlp, shift_flag=shift_flag, modulator=mod, cross_modulator=False)
+                                     token_mlp=token_mlp, shift_flag=shift_flag, modulator=mod,
+                                     cross_modulator=self.cfg.stage_has_cross_modulator(s))   # decoder stages only, model.py:1196-1245
 
-        if cross_modulator:
-            raise NotImplementedError("cross_modulator is never enabled by get_arch")
         e = embed_dim
         self.input_proj = InputProj(in_channel=dd_in, out_channel=e, kernel_size=3, stride=1, act_layer=nn.LeakyReLU)
         self.output_proj = OutputProj(in_channel=2 * e, out_channel=in_chans, kernel_size=3, stride=1)
@@ -657,6 +723,9 @@ class Uformer(nn.Module):
         if self.token_projection == 'conv' and torch.is_grad_enabled() and (self.training or x.requires_grad or any(p.requires_grad for p in self.parameters())):
             from .train import TOKEN_PROJECTION_TRAINING
             raise NotImplementedError(TOKEN_PROJECTION_TRAINING)
+        if self.cfg.cross_modulator and torch.is_grad_enabled() and (self.training or x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            from .train import CROSS_MODULATOR_TRAINING
+            raise NotImplementedError(CROSS_MODULATOR_TRAINING)
         if self.cfg.stage_windows()[4] == 4 and x.dim() == 4:     # built for 64x64 patches: 4 downsamplings x the bottleneck's window 4
             for name, n in (("H", x.shape[2]), ("W", x.shape[3])):
                 if n % 64 or n <= 0:
@@ -773,6 +842,9 @@ class Uformer(nn.Module):
             # ConvProjection: three depthwise 3x3 convolutions in front of the q | k | v GEMM (27 taps per channel, model.py:373-377)
             total += self.cfg.depths[s] * L * dims[s] * (12 * dims[s] + 2 * wins[s] ** 2 + (0 if self.cfg.mlp_is_ffn() else 36)
                                                          + (27 if self.cfg.token_projection == 'conv' else 0))
+            if self.cfg.stage_has_cross_modulator(s):
+                # cross attention (model.py:600-618): to_q and proj over the L tokens, to_kv over the 64 learned tokens, q k^T and attn v against 64 keys
+                total += self.cfg.depths[s] * (2 * L * dims[s] * dims[s] + 2 * 64 * dims[s] * dims[s] + 2 * L * dims[s] * 64)
         for s in range(4):
             L = (r // div[s]) ** 2
             total += (L // 4) * dims[s] * 2 * dims[s] * 16
@@ -923,10 +995,11 @@ class UNet(nn.Module):
 
 
 def get_arch(arch: str, train_ps: int = 128, dd_in: int = 3, embed_dim: int = 32, compute_dtype=torch.bfloat16,
-             token_projection: str = 'linear') -> nn.Module:
+             token_projection: str = 'linear', cross_modulator: bool = False) -> nn.Module:
     """utils/model_utils.py:56-81 ``get_arch(opt)`` with the option fields as arguments (``token_projection``: its hard-coded 'linear', or
-    'conv' for the paper's ablation row)."""
-    common = dict(win_size=8, token_projection=token_projection, token_mlp='leff', modulator=True, compute_dtype=compute_dtype)
+    'conv' for the paper's ablation row; ``cross_modulator``: its hard-coded False, or True for the cross-modulator variant, inference only)."""
+    common = dict(win_size=8, token_projection=token_projection, token_mlp='leff', modulator=True, compute_dtype=compute_dtype,
+                  cross_modulator=cross_modulator)
     if arch == 'Uformer':
         return Uformer(img_size=train_ps, embed_dim=embed_dim, **common)
     if arch == 'Uformer_T':

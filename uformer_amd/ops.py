@@ -335,6 +335,30 @@ def ffn(x: Tensor, gamma: Tensor, beta: Tensor, w1: Tensor, b1: Tensor, w2: Tens
     return x
 
 
+def cross_attn(x: Tensor, wq: Tensor, bq: Tensor, k: Tensor, vt: Tensor, wp: Tensor, bp: Tensor, C: Optional[int] = None) -> Tensor:
+    """The cross-modulator attention of a decoder block, IN PLACE on ``x``: x[m, :C] += proj(softmax((x[m, :C] wq^T + bq) hd^-0.5 . k_h^T) v_h)
+    (model.py:945-949, :549-595; uf_cross_attn_fwd).  x f32 (M, ld) contiguous rows on the GPU with the channels in columns [0, C) (``C`` default:
+    ld), M a multiple of 64; wq, wp T (C, C) row-major (packed fragment-major here); k T (heads, 64, hd) unscaled and vt T (heads, hd, 64) =
+    to_kv(cross_modulator.weight) (packing.pack_cross); bq, bp f32 (C,).  Returns x."""
+    _dev(x, wq, bq, k, vt, wp, bp)
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() != 2:
+        raise UformerHipError("cross_attn: x must be a contiguous f32 (M, ld) tensor (it is updated in place)")
+    dt = uf_dtype(wq.dtype)
+    M, ld = x.shape
+    Cc = ld if C is None else int(C)
+    heads, nk, hd = k.shape
+    if tuple(wq.shape) != (Cc, Cc) or tuple(wp.shape) != (Cc, Cc) or nk != 64 or heads * hd != Cc or tuple(vt.shape) != (heads, hd, 64):
+        raise UformerHipError(f"cross_attn: wq {tuple(wq.shape)} / wp {tuple(wp.shape)} / k {tuple(k.shape)} / vt {tuple(vt.shape)} do not match C = {Cc}")
+    keep = (_pack_frag(wq), _c(bq, torch.float32), _c(k, wq.dtype), _c(vt, wq.dtype), _pack_frag(_c(wp, wq.dtype)), _c(bp, torch.float32))
+    cp = _lib.CrossParams()
+    for name, tns in zip(("wq_fm", "bq", "k", "vt", "wp_fm", "bp"), keep):
+        setattr(cp, name, _ptr(tns))
+    cp.heads = int(heads)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().uf_cross_attn_fwd(cp, _ptr(x), ld, M, Cc, dt, _stream()), "uf_cross_attn_fwd")
+    return x
+
+
 def window_attention_core(q: Tensor, k: Tensor, vt: Tensor, bias_dense: Tensor, *, H: int, W: int, shift: int = 0,
                           mask: Optional[Tensor] = None) -> Tensor:
     """softmax(q k^T + bias + masks) v -> (n_windows*64, C).  model.py:498-519."""

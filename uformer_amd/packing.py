@@ -155,7 +155,44 @@ def pack_block(sd: Dict[str, Tensor], prefix: str, heads: int, shift: int, dtype
     return bp, keep
 
 
+def cross_modulator_keys(sd: Dict[str, Tensor], prefix: str) -> bool:
+    """True where the block under ``prefix`` carries a cross-modulator (``cross_modulator=True``, model.py:873-877)."""
+    return (prefix + "cross_modulator.weight") in sd
+
+
+def pack_cross(sd: Dict[str, Tensor], prefix: str, heads: int, dtype: torch.dtype):
+    """``uf_cross_params`` of the block under ``prefix``: returns (CrossParams, keepalive dict); a block without a cross-modulator gives the
+    all-NULL entry ``uf_uformer_fwd`` skips.  k and v^T are ``to_kv(cross_modulator.weight)`` (model.py:436-441 with attn_kv) evaluated in f32 and
+    then rounded to ``dtype``: 64 rows that depend on parameters only, so they are projected here, once per pack, and not per forward.  k is NOT
+    scaled (the kernel scales q); ``norm_cross`` is never read (model.py:947-948)."""
+    cp = _lib.CrossParams()
+    if not cross_modulator_keys(sd, prefix):
+        return cp, {}
+    g = lambda k: sd[prefix + k].detach()  # noqa: E731
+    emb = g("cross_modulator.weight").float()
+    n, C = emb.shape
+    if n != 64 or C % heads or C // heads not in (16, 32):
+        raise NotImplementedError(f"cross_modulator: built for 64 learned tokens and head_dim 16 or 32 (uf_cross_attn_fwd); this block has {n} tokens, "
+                                  f"width {C} and {heads} heads")
+    hd = C // heads
+    kv = torch.nn.functional.linear(emb, g("cross_attn.qkv.to_kv.weight").float(), g("cross_attn.qkv.to_kv.bias").float())      # (64, 2C) = k | v
+    keep: Dict[str, Tensor] = {
+        "wq_fm": pack_frag(g("cross_attn.qkv.to_q.weight"), dtype),
+        "bq": g("cross_attn.qkv.to_q.bias").float().clone().contiguous(),
+        "k": kv[:, :C].reshape(64, heads, hd).permute(1, 0, 2).to(dtype).contiguous(),          # [heads][64][hd]
+        "vt": kv[:, C:].reshape(64, heads, hd).permute(1, 2, 0).to(dtype).contiguous(),         # [heads][hd][64]
+        "wp_fm": pack_frag(g("cross_attn.proj.weight"), dtype),
+        "bp": g("cross_attn.proj.bias").float().clone().contiguous(),
+    }
+    for name, tns in keep.items():
+        setattr(cp, name, tns.data_ptr())
+    cp.heads = int(heads)
+    return cp, keep
+
+
 def pack_block4(sd: Dict[str, Tensor], prefix: str, heads: int, dtype: torch.dtype):
+    if cross_modulator_keys(sd, prefix):
+        raise NotImplementedError("cross_modulator is not built for 4x4-window blocks (the bottleneck of an img_size-64 model)")
     """``uf_block4_params`` of a 4x4-window block (row-major T weights, the (heads, 49) bias table): returns (Block4Params, keepalive)."""
     if conv_projection_keys(sd, prefix):
         raise NotImplementedError("token_projection='conv' is not built for 4x4-window blocks (the bottleneck of an img_size-64 model)")
@@ -199,6 +236,9 @@ class PackedModel:
         # slots stay zeroed (the whole-model entry skips them)
         self.win4 = wins[4] == 4
         self.bneck = (_lib.Block4Params * max(1, cfg.depths[4]))() if self.win4 else None
+        # cross-modulator (decoder stages of a model built with cross_modulator=True): one uf_cross_params per block, aligned with `blocks`;
+        # without the flag the descriptor's pointer stays NULL and the forward is the same launches as before
+        self.cross = (_lib.CrossParams * n_blocks)() if getattr(cfg, "cross_modulator", False) else None
         i = 0
         for s in range(9):
             for b in range(cfg.depths[s]):
@@ -208,6 +248,10 @@ class PackedModel:
                 else:
                     bp, keep = pack_block(sd, f"{STAGES[s]}.blocks.{b}.", cfg.num_heads[s], shifts[s][b], dtype)
                     self.blocks[i] = bp
+                    if self.cross is not None:
+                        cp, ckeep = pack_cross(sd, f"{STAGES[s]}.blocks.{b}.", cfg.num_heads[s], dtype)
+                        self.cross[i] = cp
+                        self.keep.append(ckeep)
                 self.keep.append(keep)
                 i += 1
         d = _lib.ModelDesc()
@@ -215,6 +259,8 @@ class PackedModel:
         for s in range(9):
             d.depths[s] = cfg.depths[s]
         d.blocks = C.cast(self.blocks, C.POINTER(_lib.BlockParams))
+        if self.cross is not None:
+            d.cross = C.cast(self.cross, C.POINTER(_lib.CrossParams))
         g = {
             "in_w27": pack_input_proj(sd["input_proj.proj.0.weight"]),
             "in_b": sd["input_proj.proj.0.bias"].detach().float().clone().contiguous(),

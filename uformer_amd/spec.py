@@ -34,6 +34,7 @@ class UformerConfig:
     shift_flag: bool = True
     token_mlp: str = "leff"      # 'leff' (LeFF) or 'ffn' / 'mlp' (Mlp: fc1 -> GELU -> fc2, model.py:890-893)
     token_projection: str = "linear"   # 'linear' (LinearProjection) or 'conv' (ConvProjection: three SepConv2d per window, model.py:381-410)
+    cross_modulator: bool = False      # decoder blocks attend to 64 learned tokens in front of their window attention (model.py:873-877, :945-949)
 
     def mlp_is_ffn(self) -> bool:
         return self.token_mlp in ("ffn", "mlp")
@@ -51,6 +52,10 @@ class UformerConfig:
     def stage_has_modulator(self, s: int) -> bool:
         """Only decoder stages receive ``modulator`` (model.py:1197,1213,1229,1245)."""
         return self.modulator and s >= 5
+
+    def stage_has_cross_modulator(self, s: int) -> bool:
+        """Only decoder stages receive ``cross_modulator`` (model.py:1197,1213,1229,1245)."""
+        return self.cross_modulator and s >= 5
 
     def stage_windows(self) -> List[int]:
         """Constructor-time window of each stage: ``win_size``, clamped to the stage's resolution where that is not larger
@@ -115,15 +120,27 @@ def arch_config(name: str, img_size: int = 256, dd_in: int = 3) -> UformerConfig
 # ---- state_dict layout ------------------------------------------------------------------
 def block_spec(prefix: str, C: int, heads: int, win: int, modulator: bool,
                mlp_ratio: float = 4.0, mod_win: int = None, token_mlp: str = "leff",
-               token_projection: str = "linear") -> Iterator[Tuple[str, Tuple[int, ...], str]]:
+               token_projection: str = "linear", cross_modulator: bool = False) -> Iterator[Tuple[str, Tuple[int, ...], str]]:
     """(key, shape, kind) of one LeWinTransformerBlock, in registration order.  ``win``: the block's (clamped) window;
     ``mod_win`` (default ``win``): the unclamped window the modulator embedding is sized by (model.py:868-869);
     ``token_mlp``: 'leff', or 'ffn' / 'mlp' for the reference's Mlp (``mlp.fc1`` / ``mlp.fc2``, model.py:623-631);
-    ``token_projection``: 'linear', or 'conv' for the reference's ConvProjection (``attn.qkv.to_{q,k,v}.{depthwise,pointwise}``, model.py:344-392)."""
+    ``token_projection``: 'linear', or 'conv' for the reference's ConvProjection (``attn.qkv.to_{q,k,v}.{depthwise,pointwise}``, model.py:344-392);
+    ``cross_modulator``: the block carries ``cross_modulator`` / ``cross_attn`` / ``norm_cross`` (model.py:873-877; ``cross_attn`` is an Attention, whose
+    projection is a LinearProjection whatever ``token_projection`` says, :558; ``norm_cross`` is registered and never read, :947-948)."""
     hid = int(C * mlp_ratio)
+    mw = win if mod_win is None else mod_win
     if modulator:
-        mw = win if mod_win is None else mod_win
         yield prefix + "modulator.weight", (mw * mw, C), "embedding"
+    if cross_modulator:
+        yield prefix + "cross_modulator.weight", (mw * mw, C), "embedding"
+        yield prefix + "cross_attn.qkv.to_q.weight", (C, C), "linear_w"
+        yield prefix + "cross_attn.qkv.to_q.bias", (C,), "linear_b"
+        yield prefix + "cross_attn.qkv.to_kv.weight", (2 * C, C), "linear_w"
+        yield prefix + "cross_attn.qkv.to_kv.bias", (2 * C,), "linear_b"
+        yield prefix + "cross_attn.proj.weight", (C, C), "linear_w"
+        yield prefix + "cross_attn.proj.bias", (C,), "linear_b"
+        yield prefix + "norm_cross.weight", (C,), "ln_w"
+        yield prefix + "norm_cross.bias", (C,), "ln_b"
     yield prefix + "norm1.weight", (C,), "ln_w"
     yield prefix + "norm1.bias", (C,), "ln_b"
     yield prefix + "attn.relative_position_bias_table", ((2 * win - 1) ** 2, heads), "rpb"
@@ -172,7 +189,7 @@ def state_dict_spec(cfg: UformerConfig) -> List[Tuple[str, Tuple[int, ...], str]
         for i in range(cfg.depths[s]):
             spec.extend(block_spec(f"{STAGES[s]}.blocks.{i}.", dims[s], cfg.num_heads[s],
                                    wins[s], cfg.stage_has_modulator(s), cfg.mlp_ratio, mod_win=cfg.win_size, token_mlp=cfg.token_mlp,
-                                   token_projection=cfg.token_projection))
+                                   token_projection=cfg.token_projection, cross_modulator=cfg.stage_has_cross_modulator(s)))
 
     for s in range(4):
         stage(s)

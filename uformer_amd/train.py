@@ -216,10 +216,17 @@ TOKEN_PROJECTION_TRAINING = ("token_projection='conv' runs inference only: train
                              "the ConvProjection yet; run it in eval() under torch.no_grad()")
 
 
+CROSS_MODULATOR_TRAINING = ("cross_modulator=True runs inference only: training (autograd, the training tape, use_checkpoint) has no backward for the "
+                            "shared-key cross attention yet; run it in eval() under torch.no_grad()")
+
+
 def refuse_conv_projection(p: Dict[str, Tensor], prefix: str = "") -> None:
-    """Training packs are built for the LinearProjection; a ConvProjection block (told by its parameter names) is refused by name."""
+    """Training packs are built for the LinearProjection without a cross-modulator; a ConvProjection block or a block with ``cross_attn.*``
+    parameters (told by its parameter names) is refused by name."""
     if packing.conv_projection_keys(p, prefix):
         raise NotImplementedError(TOKEN_PROJECTION_TRAINING)
+    if packing.cross_modulator_keys(p, prefix):
+        raise NotImplementedError(CROSS_MODULATOR_TRAINING)
 
 
 def block_is_mlp(p: Dict[str, Tensor], prefix: str = "") -> bool:
@@ -609,6 +616,8 @@ class UformerTape:
         self.sd, self.cfg, self.T, self.drop = sd, cfg, dtype, drop_scales
         if getattr(cfg, "token_projection", "linear") != "linear":
             raise NotImplementedError(TOKEN_PROJECTION_TRAINING)
+        if getattr(cfg, "cross_modulator", False):
+            raise NotImplementedError(CROSS_MODULATOR_TRAINING)
         if recompute is None and os.environ.get("UF_TRAIN_RECOMPUTE") is not None:       # A/B switch: 0 = keep every intermediate, 1 = always recompute
             recompute = os.environ["UF_TRAIN_RECOMPUTE"] != "0"
         # None = decided in forward() from the batch and the free device memory (2-byte operand types; f32 always keeps its intermediates)
