@@ -273,6 +273,11 @@ int uf_input_proj_fwd(const float* img, const float* w27, const float* bias, flo
 int uf_output_proj_fwd(const float* x, int ld_x, const float* w, const float* bias,
                        const float* img, float* out, int B, int H, int W, int C2, int add_img,
                        void* stream);
+/* The same with Cout output planes, 1..4 (Uformer(in_chans=Cout): raw planes, packed Bayer, ...): out f32 NCHW (B,Cout,H,W),
+ * w f32[Cout][9][C2], bias f32[Cout], img (read when add_img) f32 (B,Cout,H,W).  uf_output_proj_fwd is its Cout = 3 case. */
+int uf_output_proj_c_fwd(const float* x, int ld_x, const float* w, const float* bias,
+                         const float* img, float* out, int B, int H, int W, int C2, int Cout, int add_img,
+                         void* stream);
 
 /* ---- a15: backward building blocks (autograd of a5 / a10 in the reference; closed forms in
  * oracle/uformer_oracle_bwd.py, which is pinned to the reference's autograd).  First members of the family; the
@@ -369,8 +374,8 @@ int uf_col2im(const void* dcols, int ldc, float* dx, int ld_dx, int B, int H, in
               int nchw, int accumulate, uf_dtype dtype, void* stream);
 
 /* backward of the two full-resolution 3x3 stride-1 pad-1 convolutions, all f32 (InputProj 3 -> E with its LeakyReLU, model.py:771-800;
- * OutputProj 2E -> 3, model.py:803-827).  Two forms: (token rows x, Cin % 4 == 0, Cout <= 4) and (x_nchw = 1: NCHW image, Cin <= 4,
- * Cout 16, 32 or 64).  dy f32[B*H*W][Cout] token rows; act_out (InputProj form only, or NULL): the layer's stored OUTPUT rows, the
+ * OutputProj 2E -> 3, model.py:803-827).  Two forms: (token rows x, Cin % 4 == 0, Cout <= 4) and (x_nchw = 1: NCHW image, Cin <= 8,
+ * Cout 16, 32 or 64), both with Cin * Cout * 9 <= 2304 (the weights sit in LDS / registers).  dy f32[B*H*W][Cout] token rows; act_out (InputProj form only, or NULL): the layer's stored OUTPUT rows, the
  * gradient is first multiplied by LeakyReLU'(slope) taken from its sign; w (Cout,Cin,3,3) as in the state_dict.
  * dx (NULL to skip) in the layout of x; dW (Cout,Cin,3,3); db (Cout).  Sums over pixels: per-block partials added in block order. */
 size_t uf_conv3x3_bwd_workspace_bytes(int B, int H, int W, int Cin, int Cout);
@@ -536,6 +541,10 @@ int uf_crop_clamp_canvas(const float* canvas, float* out, int B, int C, int h, i
  * on the device; out f32 (B,3,ps,ps).  Call it twice with the same meta for the clean / noisy pair. */
 int uf_crop_augment(const void* src, int src_is_u8, int src_hwc, float* out, const int* meta, int B, int N, int H, int W,
                     int ps, void* stream);
+/* The same for frames of C channels, (N,H,W,C) or (N,C,H,W) -> out f32 (B,C,ps,ps): the eight transforms act on the spatial axes only.
+ * Call it with the same meta for an input of dd_in channels and its target of in_chans.  uf_crop_augment is its C = 3 case. */
+int uf_crop_augment_c(const void* src, int src_is_u8, int src_hwc, float* out, const int* meta, int B, int N, int C, int H, int W,
+                      int ps, void* stream);
 /* MixUp_AUG.aug (utils/dataset_utils.py:37-53): out[b] = lam[b] x[b] + (1 - lam[b]) x[perm[b]]; out must not alias x. */
 int uf_mixup(const float* x, float* out, const float* lam, const int* perm, int B, long long per_sample, void* stream);
 
@@ -583,7 +592,8 @@ typedef struct uf_model_desc {
 } uf_model_desc;
 
 size_t uf_uformer_workspace_bytes(const uf_model_desc* d, int B, int H, int W, uf_dtype dtype);
-/* img, out: f32 NCHW (B,dd_in,H,W) / (B,in_chans,H,W).  H and W each a positive multiple of 128 (H != W allowed; stage s runs
+/* img, out: f32 NCHW (B,dd_in,H,W) / (B,in_chans,H,W), dd_in 1..8 and in_chans 1..4; the input is added to the output (global residual,
+ * model.py:1305) exactly when dd_in == 3, and then in_chans must be 3.  H and W each a positive multiple of 128 (H != W allowed; stage s runs
  * at (H / 2^k, W / 2^k)).
  * All work is ordered on `stream`: for B >= 8 the library cuts the batch in two and runs the second half on an
  * internal side stream forked from / joined back into `stream` with events (kernel ramps and tails of the halves

@@ -143,6 +143,7 @@ SIGNATURES = {
     "uf_upsample_fwd": (I, [P, I, P, P, P, I, I, I, I, I, I, I, P]),
     "uf_input_proj_fwd": (I, [P, P, P, P, I, I, I, I, I, I, P]),
     "uf_output_proj_fwd": (I, [P, I, P, P, P, P, I, I, I, I, I, P]),
+    "uf_output_proj_c_fwd": (I, [P, I, P, P, P, P, I, I, I, I, I, I, P]),
     "uf_rows_sum_workspace_bytes": (c_size_t, [I, I]),
     "uf_rows_sum": (I, [P, I, P, I, I, I, P, c_size_t, P]),
     "uf_rpb_table_grad": (I, [P, P, I, P]),
@@ -177,6 +178,7 @@ SIGNATURES = {
     "uf_expand_canvas": (I, [P, P, P, I, I, I, I, I, I, P]),
     "uf_crop_clamp_canvas": (I, [P, P, I, I, I, I, I, I, I, P]),
     "uf_crop_augment": (I, [P, I, I, P, P, I, I, I, I, I, P]),
+    "uf_crop_augment_c": (I, [P, I, I, P, P, I, I, I, I, I, I, P]),
     "uf_mixup": (I, [P, P, P, P, I, C.c_longlong, P]),
     "uf_uformer_workspace_bytes": (c_size_t, [C.POINTER(ModelDesc), I, I, I, I]),
     "uf_uformer_fwd": (I, [C.POINTER(ModelDesc), P, P, I, I, I, I, P, c_size_t, P]),

@@ -2455,7 +2455,7 @@ extern "C" int uf_qkv_grad_merge(const void* dq, const void* dk, const void* dvt
 namespace uf {
 namespace {
 
-constexpr int CB_MAXW = 2048;        // Cout * Cin * 9 of the two layers: 864 and 1728
+constexpr int CB_MAXW = 2304;        // Cout * Cin * 9 of the two layers: 864 and 1728 for RGB; the widest stem taken here is 8 planes into 32 channels (2304 floats, 9 KiB of LDS)
 
 __device__ __forceinline__ float leaky_mask(const float* act, size_t i, float slope) { return act ? (act[i] > 0.f ? 1.f : slope) : 1.f; }   // torch: x > 0 ? g : g * slope; sign(out) = sign(x)
 
@@ -2632,7 +2632,7 @@ __global__ __launch_bounds__(192) void conv3x3_wgrad_wide_in_kernel(const float*
 // Weight gradient, WIDE output side (InputProj: Cin = 3 NCHW image, Cout = 32, LeakyReLU' folded in).  Block = one wave;
 // lane = (pixel slot, co): the 64 / Cout slots each walk a contiguous run of the row (Cout 16, 32 or 64).  dyeff[p][co] is the
 // coalesced load; the image values around p are the same address for all lanes of a slot.  Partials as above.
-template <int S>   // S = Cin <= 4
+template <int S>   // S = Cin <= 8
 __global__ __launch_bounds__(64) void conv3x3_wgrad_wide_out_kernel(const float* __restrict__ img, const float* __restrict__ dy, const float* __restrict__ act, float slope,
                                                                     float* __restrict__ partial, int B, int H, int W, int Cout, int rows_per_block) {
     const int lane = threadIdx.x;
@@ -2713,17 +2713,23 @@ extern "C" int uf_conv3x3_bwd(const float* x, int x_nchw, const float* dy, const
                               int B, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes, void* stream) {
     UF_REQUIRE(x && dy && w && dW && db && ws, UF_ERR_NULL, "uf_conv3x3_bwd: null pointer");
     const bool wide_in = Cout <= 4 && !x_nchw && Cin % 4 == 0;
-    const bool wide_out = Cin <= 4 && x_nchw && (Cout == 16 || Cout == 32 || Cout == 64);
+    const bool wide_out = Cin <= 8 && x_nchw && (Cout == 16 || Cout == 32 || Cout == 64);
     UF_REQUIRE(B > 0 && H > 0 && W > 1 && (wide_in || wide_out) && Cin * Cout * 9 <= CB_MAXW, UF_ERR_UNSUPPORTED,
-               "uf_conv3x3_bwd: Cin=%d Cout=%d nchw=%d: supported are (token rows, Cin %% 4 == 0, Cout <= 4) and (NCHW, Cin <= 4, Cout 16, 32 or 64)", Cin, Cout, x_nchw);
+               "uf_conv3x3_bwd: Cin=%d Cout=%d nchw=%d: supported are (token rows, Cin %% 4 == 0, Cout <= 4) and (NCHW, Cin <= 8, Cout 16, 32 or 64), Cin * Cout * 9 <= %d", Cin, Cout, x_nchw, CB_MAXW);
     UF_REQUIRE(!act_out || wide_out, UF_ERR_UNSUPPORTED, "uf_conv3x3_bwd: the LeakyReLU mask is folded on the InputProj form only");
     const size_t need = uf_conv3x3_bwd_workspace_bytes(B, H, W, Cin, Cout);
     UF_REQUIRE(ws_bytes >= need, UF_ERR_WORKSPACE, "uf_conv3x3_bwd: workspace too small: %zu < %zu", ws_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     if (dx) {
-        if (wide_in && !act_out && W % 16 == 0 && Cout == 3 && ((uintptr_t)dx % 16) == 0) {    // the OutputProj form: walking kernel
+        if (wide_in && !act_out && W % 16 == 0 && ((uintptr_t)dx % 16) == 0) {    // the OutputProj form: walking kernel, one instantiation per plane count
             const long long n = (long long)B * H * (W / 16) * (Cin / 4);
-            hipLaunchKernelGGL((conv3x3_dx_walk_kernel<3, 16>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dy, w, dx, B, H, W, Cin);
+            const dim3 g((unsigned)((n + 255) / 256));
+            switch (Cout) {
+                case 1: hipLaunchKernelGGL((conv3x3_dx_walk_kernel<1, 16>), g, dim3(256), 0, st, dy, w, dx, B, H, W, Cin); break;
+                case 2: hipLaunchKernelGGL((conv3x3_dx_walk_kernel<2, 16>), g, dim3(256), 0, st, dy, w, dx, B, H, W, Cin); break;
+                case 3: hipLaunchKernelGGL((conv3x3_dx_walk_kernel<3, 16>), g, dim3(256), 0, st, dy, w, dx, B, H, W, Cin); break;
+                default: hipLaunchKernelGGL((conv3x3_dx_walk_kernel<4, 16>), g, dim3(256), 0, st, dy, w, dx, B, H, W, Cin); break;
+            }
         } else {
             const int grid = grid1d((long long)B * H * W * ((Cin + 3) / 4));
             hipLaunchKernelGGL(conv3x3_dx_kernel, dim3(grid), dim3(256), 0, st, dy, act_out, slope, w, dx, B, H, W, Cin, Cout, x_nchw);
@@ -2747,7 +2753,11 @@ extern "C" int uf_conv3x3_bwd(const float* x, int x_nchw, const float* dy, const
             case 1: hipLaunchKernelGGL(conv3x3_wgrad_wide_out_kernel<1>, dim3(blocks), dim3(64), 0, st, x, dy, act_out, slope, part, B, H, W, Cout, rpb); break;
             case 2: hipLaunchKernelGGL(conv3x3_wgrad_wide_out_kernel<2>, dim3(blocks), dim3(64), 0, st, x, dy, act_out, slope, part, B, H, W, Cout, rpb); break;
             case 3: hipLaunchKernelGGL(conv3x3_wgrad_wide_out_kernel<3>, dim3(blocks), dim3(64), 0, st, x, dy, act_out, slope, part, B, H, W, Cout, rpb); break;
-            default: hipLaunchKernelGGL(conv3x3_wgrad_wide_out_kernel<4>, dim3(blocks), dim3(64), 0, st, x, dy, act_out, slope, part, B, H, W, Cout, rpb); break;
+            case 4: hipLaunchKernelGGL(conv3x3_wgrad_wide_out_kernel<4>, dim3(blocks), dim3(64), 0, st, x, dy, act_out, slope, part, B, H, W, Cout, rpb); break;
+            case 5: hipLaunchKernelGGL(conv3x3_wgrad_wide_out_kernel<5>, dim3(blocks), dim3(64), 0, st, x, dy, act_out, slope, part, B, H, W, Cout, rpb); break;
+            case 6: hipLaunchKernelGGL(conv3x3_wgrad_wide_out_kernel<6>, dim3(blocks), dim3(64), 0, st, x, dy, act_out, slope, part, B, H, W, Cout, rpb); break;
+            case 7: hipLaunchKernelGGL(conv3x3_wgrad_wide_out_kernel<7>, dim3(blocks), dim3(64), 0, st, x, dy, act_out, slope, part, B, H, W, Cout, rpb); break;
+            default: hipLaunchKernelGGL(conv3x3_wgrad_wide_out_kernel<8>, dim3(blocks), dim3(64), 0, st, x, dy, act_out, slope, part, B, H, W, Cout, rpb); break;
         }
     }
     if (int rc = check_launch("conv3x3_wgrad")) return rc;

@@ -392,10 +392,12 @@ __global__ __launch_bounds__(256) void input_proj_kernel(const float* __restrict
 // so the side-stream images of the model's two half-batch streams came out wrong (tests/test_gpu_model.py:136).  With the moves only the clean
 // `op_sel_hi:[1,0,1]` broadcast form is generated: 0 wrong outputs in 210 co-run launches (profiles/r04_run18.txt).
 __global__ void empty_kernel() {}
-template <int EG>                                   // lanes per pixel = E / 4 (8 for E = 32, 4 for E = 16)
+// CIN = dd_in of the model (3 for RGB; 1, 2, 4, 6 for raw planes, packed Bayer, image + map, dual-pixel pairs): it sizes the LDS tile
+// [CIN][6][RS] (at most 6 x 6 x 132 floats) and the trip count of the channel loop, nothing else.
+template <int EG, int CIN>                          // lanes per pixel = E / 4 (8 for E = 32, 4 for E = 16)
 __global__ __launch_bounds__(256, 4) void input_proj2_kernel(const float* __restrict__ img, const float* __restrict__ w27, const float* __restrict__ bias,
                                                           float* __restrict__ out, int ld_o, int B, int H, int W) {
-    constexpr int CIN = 3, E = EG * 4, SL = 8, NSTRIP = 64 / EG, TW = NSTRIP * SL, RS = TW + 4;     // row stride in floats (16-byte multiple; index j = pixel x0 - 1 + j)
+    constexpr int E = EG * 4, SL = 8, NSTRIP = 64 / EG, TW = NSTRIP * SL, RS = TW + 4;     // row stride in floats (16-byte multiple; index j = pixel x0 - 1 + j)
     __shared__ __attribute__((aligned(16))) float Is[CIN][6][RS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int x0 = blockIdx.x * TW, y0 = blockIdx.y * 4, b = blockIdx.z;
@@ -443,14 +445,20 @@ __global__ __launch_bounds__(256, 4) void input_proj2_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------
-// a14: OutputProj conv3x3(C2->3) (+ global residual), token rows -> NCHW image (model.py:869-890, :1305).
+// a14: OutputProj conv3x3(C2->CO) (+ global residual), token rows -> NCHW image (model.py:869-890, :1305).
 // LPP = C2/4 lanes share a column strip of OP_R vertically adjacent pixels, each lane owning 4 input
-// channels; per kx the 9 weight vectors (3 ky x 3 outputs) are loaded once and the OP_R + 2 token rows of
-// the strip feed 3 taps each: 45 loads per 432 dot-FMAs instead of 36 per 108.  DPP all-reduce over the
-// LPP lanes at the end; lanes 0..2 of the group store one output plane each.
+// channels; per kx the 3 CO weight vectors (3 ky x CO outputs) are loaded once and the OP_R + 2 token rows of
+// the strip feed 3 taps each: at CO = 3, 45 loads per 432 dot-FMAs instead of 36 per 108.  DPP all-reduce over the
+// LPP lanes at the end; lanes 0..CO-1 of the group store one output plane each (LPP >= 4 >= CO).
+// CO = in_chans of the model (1..4; 3 for RGB): it sizes the accumulators, the weight vectors per tap, the storing lanes and the
+// output's plane stride -- per output plane the sums are the same FMAs in the same order at every CO.
 // ---------------------------------------------------------------------------------------
 constexpr int OP_R = 4;
-template <int LPP>
+// lane `sub` (< CO where it stores) picks its plane by a select chain over named elements: indices past CO - 1 repeat the last plane, so the chain
+// folds to CO - 1 selects (a helper taking the row by reference left the sums in scratch)
+#define UF_PICK_PLANE(A, SUB, CO) \
+    (SUB == 0 ? A[0] : (SUB == 1 ? A[CO > 1 ? 1 : 0] : (SUB == 2 ? A[CO > 2 ? 2 : CO - 1] : A[CO - 1])))
+template <int LPP, int CO>
 __global__ __launch_bounds__(256) void output_proj_kernel(const float* __restrict__ x, int ld_x, const float* __restrict__ w,
                                                           const float* __restrict__ bias, const float* __restrict__ img,
                                                           float* __restrict__ out, int B, int H, int W, int add_img) {
@@ -460,11 +468,11 @@ __global__ __launch_bounds__(256) void output_proj_kernel(const float* __restric
     const int sub = (int)(idx % LPP);
     const bool live = idx / LPP < (unsigned)W;
     const int xw = live ? (int)(idx / LPP) : 0, y0 = blockIdx.y * OP_R, b = blockIdx.z;
-    f32x4 acc[OP_R][3];   // per-lane partial sums stay 4 channels wide (pure FMAs); one horizontal add at the end
+    f32x4 acc[OP_R][CO];   // per-lane partial sums stay 4 channels wide (pure FMAs); one horizontal add at the end
 #pragma unroll
     for (int r = 0; r < OP_R; ++r)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) acc[r][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < CO; ++c) acc[r][c] = f32x4{0.f, 0.f, 0.f, 0.f};
     int ro[OP_R + 2];
     float my[OP_R + 2];
 #pragma unroll
@@ -480,11 +488,11 @@ __global__ __launch_bounds__(256) void output_proj_kernel(const float* __restric
         const int ixr = xw + kx - 1;
         const int ix = ixr < 0 ? 0 : (ixr >= W ? W - 1 : ixr);
         const float mxk = (ixr >= 0 && ixr < W) ? 1.0f : 0.0f;
-        f32x4 wk[3][3];
+        f32x4 wk[3][CO];
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-            for (int c = 0; c < 3; ++c) wk[ky][c] = *reinterpret_cast<const f32x4*>(ws + (c * 9 + ky * 3 + kx) * C2);
+            for (int c = 0; c < CO; ++c) wk[ky][c] = *reinterpret_cast<const f32x4*>(ws + (c * 9 + ky * 3 + kx) * C2);
 #pragma unroll
         for (int hr = 0; hr < OP_R + 2; ++hr) {
             // zero padding by a 0/1 factor, loads unconditional from clamped addresses, 32-bit element offsets
@@ -494,22 +502,22 @@ __global__ __launch_bounds__(256) void output_proj_kernel(const float* __restric
                 const int r = hr - ky;
                 if (r < 0 || r >= OP_R) continue;
 #pragma unroll
-                for (int c = 0; c < 3; ++c) acc[r][c] += v * wk[ky][c];
+                for (int c = 0; c < CO; ++c) acc[r][c] += v * wk[ky][c];
             }
         }
     }
-    float a[OP_R][3];
+    float a[OP_R][CO];
 #pragma unroll
     for (int r = 0; r < OP_R; ++r)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) a[r][c] = allreduce<RedSum, LPP>((acc[r][c][0] + acc[r][c][1]) + (acc[r][c][2] + acc[r][c][3]));
-    if (live && sub < 3) {
+        for (int c = 0; c < CO; ++c) a[r][c] = allreduce<RedSum, LPP>((acc[r][c][0] + acc[r][c][1]) + (acc[r][c][2] + acc[r][c][3]));
+    if (live && sub < CO) {
         const float bs = bias[sub];
 #pragma unroll
         for (int r = 0; r < OP_R; ++r) {
             if (y0 + r >= H) break;
-            const size_t o = ((size_t)b * 3 + sub) * H * W + (size_t)(y0 + r) * W + xw;
-            float v = (sub == 0 ? a[r][0] : (sub == 1 ? a[r][1] : a[r][2])) + bs;
+            const size_t o = ((size_t)b * CO + sub) * H * W + (size_t)(y0 + r) * W + xw;
+            float v = UF_PICK_PLANE(a[r], sub, CO) + bs;
             if (add_img) v += img[o];  // return x + y (model.py:1305)
             out[o] = v;
         }
@@ -524,7 +532,7 @@ __global__ __launch_bounds__(256) void output_proj_kernel(const float* __restric
 // the XCD-aware tile order of leff2 (neighbouring tiles share halo rows in one XCD's L2), and the products run from LDS: same
 // per-lane partial sums, the same DPP all-reduce, the same order of additions as the first form -- bit-identical results.
 // ---------------------------------------------------------------------------------------
-template <int LPP>
+template <int LPP, int CO>
 __global__ __launch_bounds__(256) void output_proj2_kernel(const float* __restrict__ x, int ld_x, const float* __restrict__ w, const float* __restrict__ bias,
                                                            const float* __restrict__ img, float* __restrict__ out, int B, int H, int W, int add_img, int tiles_x, int tiles_y) {
     constexpr int C2 = LPP * 4, NCOL = 256 / LPP, NX = 2, TW = NX * NCOL, HW2 = TW + 2;
@@ -555,21 +563,21 @@ __global__ __launch_bounds__(256) void output_proj2_kernel(const float* __restri
     __syncthreads();
     const int sub = tid % LPP, col = tid / LPP;
     const float* ws = w + sub * 4;
-    const float bs = bias[sub < 3 ? sub : 0];
+    const float bs = bias[sub < CO ? sub : 0];
 #pragma unroll 1
     for (int j = 0; j < NX; ++j) {
-        f32x4 acc[OP_R][3];
+        f32x4 acc[OP_R][CO];
 #pragma unroll
         for (int r = 0; r < OP_R; ++r)
 #pragma unroll
-            for (int c = 0; c < 3; ++c) acc[r][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int c = 0; c < CO; ++c) acc[r][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
         for (int kx = 0; kx < 3; ++kx) {                   // not unrolled: nine weight vectors live at a time (the compiler otherwise hoists all 27 out of the column loop)
-            f32x4 wk[3][3];
+            f32x4 wk[3][CO];
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-                for (int c = 0; c < 3; ++c) wk[ky][c] = *reinterpret_cast<const f32x4*>(ws + (c * 9 + ky * 3 + kx) * C2);
+                for (int c = 0; c < CO; ++c) wk[ky][c] = *reinterpret_cast<const f32x4*>(ws + (c * 9 + ky * 3 + kx) * C2);
 #pragma unroll
             for (int hr = 0; hr < OP_R + 2; ++hr) {
                 const f32x4 v = *reinterpret_cast<const f32x4*>(tile + ((hr * HW2) + col + NCOL * j + kx) * C2 + sub * 4);
@@ -578,22 +586,22 @@ __global__ __launch_bounds__(256) void output_proj2_kernel(const float* __restri
                     const int r = hr - ky;
                     if (r < 0 || r >= OP_R) continue;
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) acc[r][c] += v * wk[ky][c];
+                    for (int c = 0; c < CO; ++c) acc[r][c] += v * wk[ky][c];
                 }
             }
         }
-        float a[OP_R][3];
+        float a[OP_R][CO];
 #pragma unroll
         for (int r = 0; r < OP_R; ++r)
 #pragma unroll
-            for (int c = 0; c < 3; ++c) a[r][c] = allreduce<RedSum, LPP>((acc[r][c][0] + acc[r][c][1]) + (acc[r][c][2] + acc[r][c][3]));
+            for (int c = 0; c < CO; ++c) a[r][c] = allreduce<RedSum, LPP>((acc[r][c][0] + acc[r][c][1]) + (acc[r][c][2] + acc[r][c][3]));
         const int xw = x0 + col + NCOL * j;
-        if (sub < 3 && xw < W) {
+        if (sub < CO && xw < W) {
 #pragma unroll
             for (int r = 0; r < OP_R; ++r) {
                 if (y0 + r >= H) break;
-                const size_t o = ((size_t)b * 3 + sub) * H * W + (size_t)(y0 + r) * W + xw;
-                float v = (sub == 0 ? a[r][0] : (sub == 1 ? a[r][1] : a[r][2])) + bs;
+                const size_t o = ((size_t)b * CO + sub) * H * W + (size_t)(y0 + r) * W + xw;
+                float v = UF_PICK_PLANE(a[r], sub, CO) + bs;
                 if (add_img) v += img[o];
                 out[o] = v;
             }
@@ -826,10 +834,23 @@ extern "C" int uf_input_proj_fwd(const float* img, const float* w27, const float
     // The LDS-staged second form (input_proj2_kernel: 107 -> 44 us at 16 x 256 x 256, bit-identical to the first form) is the default since the
     // packed-f32 operand-select hazard that corrupted it beside MFMA kernels was found and removed (see the kernel comment); UF_VARIANT="stem=1": first form.
     const bool v1 = variant("stem", 2) == 1;
-    if (!v1 && Cin == 3 && (E == 32 || E == 16) && (H + 3) / 4 <= 65535) {
+    // Built for the image channel counts the reference's tasks use (1, 2, 3, 4, 6); any other Cin, and E = 64, keep the first form.
+    const bool cin2 = Cin == 1 || Cin == 2 || Cin == 3 || Cin == 4 || Cin == 6;
+    if (!v1 && cin2 && (E == 32 || E == 16) && (H + 3) / 4 <= 65535) {
         const dim3 g32((W + 63) / 64, (H + 3) / 4, B), g16((W + 127) / 128, (H + 3) / 4, B);
-        if (E == 32) hipLaunchKernelGGL(input_proj2_kernel<8>, g32, dim3(256), 0, (hipStream_t)stream, img, w27, bias, out, ld_o, B, H, W);
-        else hipLaunchKernelGGL(input_proj2_kernel<4>, g16, dim3(256), 0, (hipStream_t)stream, img, w27, bias, out, ld_o, B, H, W);
+#define UF_IP2(CINV)                                                                                                                                     \
+        case CINV:                                                                                                                                       \
+            if (E == 32) hipLaunchKernelGGL((input_proj2_kernel<8, CINV>), g32, dim3(256), 0, (hipStream_t)stream, img, w27, bias, out, ld_o, B, H, W); \
+            else hipLaunchKernelGGL((input_proj2_kernel<4, CINV>), g16, dim3(256), 0, (hipStream_t)stream, img, w27, bias, out, ld_o, B, H, W);         \
+            break;
+        switch (Cin) {
+            UF_IP2(1)
+            UF_IP2(2)
+            UF_IP2(3)
+            UF_IP2(4)
+            default: UF_IP2(6)
+        }
+#undef UF_IP2
         return check_launch("input_proj");
     }
     if (px == 8) hipLaunchKernelGGL(input_proj_kernel<8>, dim3((nx + 255) / 256, H, B), dim3(256), 0, (hipStream_t)stream, img, w27, bias, out, ld_o, B, Cin, H, W, E);
@@ -837,14 +858,24 @@ extern "C" int uf_input_proj_fwd(const float* img, const float* w27, const float
     return check_launch("input_proj");
 }
 
-extern "C" int uf_output_proj_fwd(const float* x, int ld_x, const float* w, const float* bias, const float* img, float* out,
-                                  int B, int H, int W, int C2, int add_img, void* stream) {
+// Cout output planes (1..4).  uf_output_proj_fwd below is the Cout = 3 case.
+extern "C" int uf_output_proj_c_fwd(const float* x, int ld_x, const float* w, const float* bias, const float* img, float* out,
+                                    int B, int H, int W, int C2, int Cout, int add_img, void* stream) {
     UF_REQUIRE(x && w && bias && out && (!add_img || img), UF_ERR_NULL, "uf_output_proj_fwd: null pointer");
     UF_REQUIRE(B > 0 && H > 0 && W > 0 && ld_x >= C2 && ld_x % 4 == 0, UF_ERR_SHAPE, "uf_output_proj_fwd: bad shape");
+    UF_REQUIRE(Cout >= 1 && Cout <= 4, UF_ERR_UNSUPPORTED, "uf_output_proj_fwd: Cout=%d unsupported (1..4)", Cout);
     UF_REQUIRE((long long)B * H * W * ld_x < 0xffffffffLL && H / OP_R < 65535 && B <= 65535, UF_ERR_SHAPE, "uf_output_proj_fwd: tensor too large for 32-bit indexing");
     hipStream_t st = (hipStream_t)stream;
     const long long pix = (long long)B * H * W;
-    ScopedTimer tm("output_proj", 54.0 * pix * C2, 4.0 * pix * (C2 + 6), st);
+    ScopedTimer tm("output_proj", 18.0 * Cout * pix * C2, 4.0 * pix * (C2 + 2 * Cout), st);
+    // one switch over the plane count around every launch: each (LPP, CO) pair is its own kernel
+#define UF_OP_CO(LAUNCH)                                                    \
+    switch (Cout) {                                                         \
+        case 1: LAUNCH(1) break;                                            \
+        case 2: LAUNCH(2) break;                                            \
+        case 3: LAUNCH(3) break;                                            \
+        default: LAUNCH(4) break;                                           \
+    }
     {   // second form (LDS-DMA staged halo tile) where the tile fits LDS and 32-bit byte offsets address the tensor; UF_VARIANT="head=1": first form
         const bool v1 = variant("head", 2) == 1;
         if (!v1 && (C2 == 16 || C2 == 32 || C2 == 64) && (long long)B * H * W * ld_x * 4 < 0xffffff00LL) {
@@ -852,35 +883,54 @@ extern "C" int uf_output_proj_fwd(const float* x, int ld_x, const float* w, cons
             const int smem = (6 * (tw + 2) * C2 * 4 + 1023) / 1024 * 1024;      // whole DMA instructions (1 KiB each): the last one may run past the tile
             const long long nt = (long long)tiles_x * tiles_y * B;
             if (nt < 0x7fffffffLL) {
-#define UF_OP2(LPPV)                                                                                                                                  \
+#define UF_OP2(LPPV, COV)                                                                                                                             \
                 {                                                                                                                                     \
-                    auto kern = output_proj2_kernel<LPPV>;                                                                                            \
+                    auto kern = output_proj2_kernel<LPPV, COV>;                                                                                       \
                     static bool lds_done[64] = {};                                                                                                    \
                     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, lds_done, "output_proj")) return rc;                  \
                     hipLaunchKernelGGL(kern, dim3((unsigned)nt), dim3(256), smem, st, x, ld_x, w, bias, img, out, B, H, W, add_img, tiles_x, tiles_y); \
                 }
-                if (lpp == 4) UF_OP2(4) else if (lpp == 8) UF_OP2(8) else UF_OP2(16)
+#define UF_OP2_4(COV) UF_OP2(4, COV)
+#define UF_OP2_8(COV) UF_OP2(8, COV)
+#define UF_OP2_16(COV) UF_OP2(16, COV)
+                if (lpp == 4) { UF_OP_CO(UF_OP2_4) } else if (lpp == 8) { UF_OP_CO(UF_OP2_8) } else { UF_OP_CO(UF_OP2_16) }
+#undef UF_OP2_4
+#undef UF_OP2_8
+#undef UF_OP2_16
 #undef UF_OP2
                 return check_launch("output_proj");
             }
         }
     }
-#define UF_OP_CASE(LPPV)                                                                                          \
-    case LPPV * 4: {                                                                                              \
-        const unsigned nx = (unsigned)W * LPPV;                                                                   \
-        hipLaunchKernelGGL(output_proj_kernel<LPPV>, dim3((nx + 255) / 256, (H + OP_R - 1) / OP_R, B), dim3(256), 0, st, x, ld_x, \
-                           w, bias, img, out, B, H, W, add_img);                                                  \
-        break;                                                                                                    \
+#define UF_OP1(LPPV, COV)                                                                                                               \
+    {                                                                                                                                   \
+        const unsigned nx = (unsigned)W * LPPV;                                                                                         \
+        hipLaunchKernelGGL((output_proj_kernel<LPPV, COV>), dim3((nx + 255) / 256, (H + OP_R - 1) / OP_R, B), dim3(256), 0, st, x, ld_x, \
+                           w, bias, img, out, B, H, W, add_img);                                                                        \
     }
+#define UF_OP1_4(COV) UF_OP1(4, COV)
+#define UF_OP1_8(COV) UF_OP1(8, COV)
+#define UF_OP1_16(COV) UF_OP1(16, COV)
+#define UF_OP1_32(COV) UF_OP1(32, COV)
     switch (C2) {
-        UF_OP_CASE(4)
-        UF_OP_CASE(8)
-        UF_OP_CASE(16)
-        UF_OP_CASE(32)
+        case 16: UF_OP_CO(UF_OP1_4) break;
+        case 32: UF_OP_CO(UF_OP1_8) break;
+        case 64: UF_OP_CO(UF_OP1_16) break;
+        case 128: UF_OP_CO(UF_OP1_32) break;
         default:
             set_error("uf_output_proj_fwd: C2=%d unsupported (16,32,64,128)", C2);
             return UF_ERR_UNSUPPORTED;
     }
-#undef UF_OP_CASE
+#undef UF_OP1_4
+#undef UF_OP1_8
+#undef UF_OP1_16
+#undef UF_OP1_32
+#undef UF_OP1
+#undef UF_OP_CO
     return check_launch("output_proj");
+}
+
+extern "C" int uf_output_proj_fwd(const float* x, int ld_x, const float* w, const float* bias, const float* img, float* out,
+                                  int B, int H, int W, int C2, int add_img, void* stream) {
+    return uf_output_proj_c_fwd(x, ld_x, w, bias, img, out, B, H, W, C2, 3, add_img, stream);
 }

@@ -369,6 +369,15 @@ extern "C" size_t uf_uformer_workspace_bytes(const uf_model_desc* d, int B, int 
 // bneck (NULL for the standard model): the uf_block4_params of the bottleneck's depths[4] blocks, which then run on the 4x4-window path
 // (their uf_block_params entries in d->blocks are skipped)
 namespace {
+// Image channel counts (model.py:1100-1101, :1305): dd_in planes in, in_chans planes out; the global residual x + y is added exactly when
+// dd_in == 3, and then the two have to agree.
+int check_image_chans(const uf_model_desc* d) {
+    UF_REQUIRE(d->dd_in >= 1 && d->dd_in <= 8, UF_ERR_UNSUPPORTED, "uf_uformer_fwd: dd_in=%d (1..8 supported)", d->dd_in);
+    UF_REQUIRE(d->in_chans >= 1 && d->in_chans <= 4, UF_ERR_UNSUPPORTED, "uf_uformer_fwd: in_chans=%d (1..4 supported)", d->in_chans);
+    UF_REQUIRE(d->dd_in != 3 || d->in_chans == 3, UF_ERR_UNSUPPORTED, "uf_uformer_fwd: dd_in=3 adds the input to the output (global residual), so in_chans=%d must be 3",
+               d->in_chans);
+    return UF_OK;
+}
 int forward_one_stream(const uf_model_desc* d, const uf_block4_params* bneck, const float* img, float* out, int B, int H, int W, uf_dtype dtype,
                        void* ws, size_t ws_bytes, void* stream) {
     Plan pl;
@@ -377,7 +386,7 @@ int forward_one_stream(const uf_model_desc* d, const uf_block4_params* bneck, co
     UF_REQUIRE(img && out && ws && d->blocks, UF_ERR_NULL, "uf_uformer_fwd: null pointer");
     UF_REQUIRE(((uintptr_t)ws % 256) == 0, UF_ERR_ALIGN, "uf_uformer_fwd: workspace must be 256-byte aligned");
     UF_REQUIRE(ws_bytes >= pl.total, UF_ERR_WORKSPACE, "uf_uformer_fwd: workspace too small: %zu < %zu", ws_bytes, pl.total);
-    UF_REQUIRE(d->in_chans == 3, UF_ERR_UNSUPPORTED, "uf_uformer_fwd: in_chans=%d (3 supported)", d->in_chans);
+    if (int rc2 = check_image_chans(d)) return rc2;
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)ws;
     float* D[4];
@@ -434,7 +443,7 @@ int forward_one_stream(const uf_model_desc* d, const uf_block4_params* bneck, co
         if (rc) return rc;
     }
     // output projection + global residual, model.py:1304-1305
-    return uf_output_proj_fwd(x, ld, d->out_w, d->out_b, img, out, B, H, W, pl.C[8], d->dd_in == 3 ? 1 : 0, st);
+    return uf_output_proj_c_fwd(x, ld, d->out_w, d->out_b, img, out, B, H, W, pl.C[8], d->in_chans, d->dd_in == 3 ? 1 : 0, st);
 }
 
 }  // namespace
@@ -453,6 +462,7 @@ int forward_split(const uf_model_desc* d, const uf_block4_params* bneck, const f
     if (n > B) n = B;
     if (n < 2 || timing_enabled()) return forward_one_stream(d, bneck, img, out, B, H, W, dtype, ws, ws_bytes, stream);
     UF_REQUIRE(d && img && out && ws, UF_ERR_NULL, "uf_uformer_fwd: null pointer");
+    if (int rc = check_image_chans(d)) return rc;        // before the first part is enqueued: the batch offsets below use both fields
     int dev = 0;
     Lane* ss = acquire_lane(n - 1, &dev);
     UF_REQUIRE(ss, UF_ERR_LAUNCH, "uf_uformer_fwd: could not create the side streams");
@@ -469,7 +479,7 @@ int forward_split(const uf_model_desc* d, const uf_block4_params* bneck, const f
         UF_REQUIRE(ws_bytes >= off + pl.total, UF_ERR_WORKSPACE, "uf_uformer_fwd: workspace too small for %d streams", n);
         hipStream_t si = i == 0 ? st : ss->s[i - 1];
         if (i > 0) hipStreamWaitEvent(si, ss->fork, 0);
-        rc = forward_one_stream(d, bneck, img + (size_t)b0 * d->dd_in * H * W, out + (size_t)b0 * 3 * H * W, Bi, H, W, dtype, (char*)ws + off,
+        rc = forward_one_stream(d, bneck, img + (size_t)b0 * d->dd_in * H * W, out + (size_t)b0 * d->in_chans * H * W, Bi, H, W, dtype, (char*)ws + off,
                                 pl.total, si);
         if (rc && !rc_all) rc_all = rc;
         if (i > 0) {

@@ -250,10 +250,10 @@ __global__ __launch_bounds__(256) void crop_clamp_kernel(const float* __restrict
 // or f32; layout (N,H,W,3) "hwc" (what cv2 / PIL hand over) or (N,3,H,W).
 template <typename S>
 __global__ __launch_bounds__(256) void crop_aug_kernel(const S* __restrict__ src, float* __restrict__ out, const int* __restrict__ meta /* [B][4]: idx, r0, c0, k */,
-                                                       int N, int B, int H, int W, int ps, int hwc) {
-    const long long n = (long long)B * 3 * ps * ps;
+                                                       int N, int B, int C, int H, int W, int ps, int hwc) {
+    const long long n = (long long)B * C * ps * ps;
     for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long long)gridDim.x * 256) {
-        const int j = (int)(t % ps), i = (int)((t / ps) % ps), c = (int)((t / ((long long)ps * ps)) % 3), b = (int)(t / ((long long)3 * ps * ps));
+        const int j = (int)(t % ps), i = (int)((t / ps) % ps), c = (int)((t / ((long long)ps * ps)) % C), b = (int)(t / ((long long)C * ps * ps));
         // device-side metadata is clamped into the frame stack: a bad index or crop origin (user-supplied meta) reads a valid
         // pixel instead of memory outside the allocation (the host checks N, H, W, ps; the entries themselves live on the device)
         int idx = meta[b * 4], r0 = meta[b * 4 + 1], c0 = meta[b * 4 + 2];
@@ -270,7 +270,7 @@ __global__ __launch_bounds__(256) void crop_aug_kernel(const S* __restrict__ src
             default: sy = j; sx = ps - 1 - ii; break;
         }
         const size_t y = r0 + sy, x = c0 + sx;
-        const size_t o = hwc ? (((size_t)idx * H + y) * W + x) * 3 + c : (((size_t)idx * 3 + c) * H + y) * W + x;
+        const size_t o = hwc ? (((size_t)idx * H + y) * W + x) * C + c : (((size_t)idx * C + c) * H + y) * W + x;
         float v;
         if constexpr (sizeof(S) == 1) v = (float)src[o] / 255.0f; else v = (float)src[o];
         out[t] = v;
@@ -505,17 +505,22 @@ extern "C" int uf_crop_clamp_canvas(const float* canvas, float* out, int B, int 
     return crop_clamp_canvas(canvas, out, B, C, h, w, Xh, Xw, clamp01, stream, "uf_crop_clamp_canvas");
 }
 
-extern "C" int uf_crop_augment(const void* src, int src_is_u8, int src_hwc, float* out, const int* meta, int B, int N, int H, int W, int ps, void* stream) {
+// frames of C channels (the transforms act on the spatial axes only).  uf_crop_augment below is the C = 3 case.
+extern "C" int uf_crop_augment_c(const void* src, int src_is_u8, int src_hwc, float* out, const int* meta, int B, int N, int C, int H, int W, int ps, void* stream) {
     UF_REQUIRE(src && out && meta, UF_ERR_NULL, "uf_crop_augment: null pointer");
     UF_REQUIRE(B > 0 && N > 0 && ps > 0 && ps <= H && ps <= W, UF_ERR_SHAPE, "uf_crop_augment: B=%d N=%d H=%d W=%d ps=%d", B, N, H, W, ps);
-    const long long n = (long long)B * 3 * ps * ps;
+    UF_REQUIRE(C > 0, UF_ERR_SHAPE, "uf_crop_augment: C=%d", C);
+    const long long n = (long long)B * C * ps * ps;
     hipStream_t st = (hipStream_t)stream;
     {
         ScopedTimer tm("crop_augment", 0.0, (src_is_u8 ? 5.0 : 8.0) * n, st);
-        if (src_is_u8) hipLaunchKernelGGL(crop_aug_kernel<unsigned char>, dim3(grid_for(n, 1024)), dim3(256), 0, st, (const unsigned char*)src, out, meta, N, B, H, W, ps, src_hwc);
-        else hipLaunchKernelGGL(crop_aug_kernel<float>, dim3(grid_for(n, 1024)), dim3(256), 0, st, (const float*)src, out, meta, N, B, H, W, ps, src_hwc);
+        if (src_is_u8) hipLaunchKernelGGL(crop_aug_kernel<unsigned char>, dim3(grid_for(n, 1024)), dim3(256), 0, st, (const unsigned char*)src, out, meta, N, B, C, H, W, ps, src_hwc);
+        else hipLaunchKernelGGL(crop_aug_kernel<float>, dim3(grid_for(n, 1024)), dim3(256), 0, st, (const float*)src, out, meta, N, B, C, H, W, ps, src_hwc);
     }
     return check_launch("crop_augment");
+}
+extern "C" int uf_crop_augment(const void* src, int src_is_u8, int src_hwc, float* out, const int* meta, int B, int N, int H, int W, int ps, void* stream) {
+    return uf_crop_augment_c(src, src_is_u8, src_hwc, out, meta, B, N, 3, H, W, ps, stream);
 }
 extern "C" int uf_mixup(const float* x, float* out, const float* lam, const int* perm, int B, long long per_sample, void* stream) {
     UF_REQUIRE(x && out && lam && perm && x != out, UF_ERR_NULL, "uf_mixup: null pointer (out must not alias x: samples read their partner)");

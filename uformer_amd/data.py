@@ -33,15 +33,22 @@ def sample_patch_meta(batch: int, n_frames: int, H: int, W: int, ps: int, indice
 
 
 class GpuPatchLoader:
-    """clean / noisy frame stacks resident on the GPU ((N,H,W,3) uint8 as decoded, or (N,3,H,W) f32) -> training batches."""
+    """clean / noisy frame stacks resident on the GPU ((N,H,W,C) uint8 as decoded, or (N,C,H,W) f32) -> training batches.  The two stacks share
+    N, H and W; their channel counts may differ: a target of ``in_chans`` planes beside an input of ``dd_in`` (3 and 6 for dual-pixel
+    deblurring, 3 and 4 for an image with a noise map).  ``hwc``: the layout of both stacks; None guesses it from the shape (a last axis of
+    at most 8 entries beside a longer second one is the channel axis)."""
 
     def __init__(self, clean: torch.Tensor, noisy: torch.Tensor, patch_size: int, hwc: Optional[bool] = None):
-        if clean.shape != noisy.shape:
-            raise ValueError("clean / noisy stacks differ in shape")
-        self.hwc = (clean.shape[-1] == 3 and clean.shape[1] != 3) if hwc is None else hwc
+        if clean.dim() != 4 or noisy.dim() != 4:
+            raise ValueError(f"clean / noisy stacks must be 4-D, got {tuple(clean.shape)} / {tuple(noisy.shape)}")
+        if hwc is None:
+            hwc = (clean.shape[-1] == 3 and clean.shape[1] != 3) or (clean.shape[-1] <= 8 < clean.shape[1])
+        self.hwc = hwc
+        geom = (lambda t: (t.shape[0], t.shape[1], t.shape[2])) if hwc else (lambda t: (t.shape[0], t.shape[2], t.shape[3]))
+        if geom(clean) != geom(noisy):
+            raise ValueError(f"clean / noisy stacks differ in shape: {tuple(clean.shape)} / {tuple(noisy.shape)} (only the channel counts may differ)")
         self.clean, self.noisy, self.ps = clean, noisy, patch_size
-        self.N = clean.shape[0]
-        self.H, self.W = (clean.shape[1], clean.shape[2]) if self.hwc else (clean.shape[2], clean.shape[3])
+        self.N, self.H, self.W = geom(clean)
 
     def batch(self, batch_size: int, indices=None) -> Tuple[torch.Tensor, torch.Tensor]:
         meta = sample_patch_meta(batch_size, self.N, self.H, self.W, self.ps, indices).to(self.clean.device, non_blocking=True)

@@ -40,7 +40,7 @@ def crop_to_mask(restored: Tensor, h: int, w: int, clamp: bool = False) -> Tenso
 @torch.no_grad()
 def restore(model, img: Tensor, factor: float = 128.0, clamp: bool = True, canvas: str = "square") -> Tensor:
     """Restore images of any (h, w): pad to a canvas of multiples of ``factor``, run ``model``, crop back, clamp to [0,1]
-    (test/test_sidd.py:106-109).  ``img``: (B,3,h,w) float32 on the model's device.
+    (test/test_sidd.py:106-109).  ``img``: (B,dd_in,h,w) float32 on the model's device; the result has the model's ``in_chans`` planes.
 
     ``canvas="square"`` (default): the reference's protocol -- ``expand2square``, one square side X = max(h, w) rounded up to a
     multiple of ``factor``; output identical to the reference pipeline.
@@ -74,7 +74,7 @@ def restore_tiled(model, img: Tensor, tile: int = 768, min_overlap: int = 128, c
     construction -- the network's receptive field spans several hundred pixels, so a tile does not see what the full frame sees.
     The mechanics (cutting, padding, ramps, normalisation) are exact: tests/test_host_logic.py checks them to 2e-6 with a pointwise
     model; against the full-frame result of a real network only a PSNR is reported (tests/test_gpu_tail.py).
-    Overlapped-tile restoration of (B,3,h,w) images: square ``tile`` x ``tile`` windows (a multiple of 128) at evenly spaced
+    Overlapped-tile restoration of (B,dd_in,h,w) images (the result has the model's ``in_chans`` planes): square ``tile`` x ``tile`` windows (a multiple of 128) at evenly spaced
     positions with at least ``min_overlap`` pixels in common, forwarded in batches of ``max_batch`` tiles, blended with a linear
     ramp across each overlap.  An image that fits one tile takes the reference-exact ``restore`` path."""
     if tile % 128:
@@ -83,7 +83,7 @@ def restore_tiled(model, img: Tensor, tile: int = 768, min_overlap: int = 128, c
     if h <= tile and w <= tile:
         return restore(model, img, 128.0, clamp)
     ys, xs = _starts(h, tile, min_overlap), _starts(w, tile, min_overlap)
-    acc = torch.zeros((B, C, h, w), dtype=torch.float32, device=img.device)
+    acc = None            # (B, in_chans, h, w): sized by the first output, whose plane count is the model's, not the input's
     wsum = torch.zeros((1, 1, h, w), dtype=torch.float32, device=img.device)
 
     def ramp(n: int, start: int, starts: List[int], size: int) -> Tensor:
@@ -111,6 +111,8 @@ def restore_tiled(model, img: Tensor, tile: int = 768, min_overlap: int = 128, c
                 t = torch.nn.functional.pad(t, (0, tile - tw, 0, tile - th))
             tiles.append(t)
         out = model(torch.cat(tiles, 0).contiguous())
+        if acc is None:
+            acc = torch.zeros((B, out.shape[1], h, w), dtype=torch.float32, device=img.device)
         for k, (y, x) in enumerate(chunk):
             th, tw = min(tile, h - y), min(tile, w - x)
             wy, wx = ramp(h, y, ys, th), ramp(w, x, xs, tw)

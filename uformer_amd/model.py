@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import _lib, ops, packing
 from ._lib import UformerHipError
-from .spec import STAGES, UformerConfig, relative_position_index
+from .spec import MAX_IN_CHANS, STAGES, UformerConfig, check_image_chans, relative_position_index
 from .train import block_hw
 
 Tensor = torch.Tensor
@@ -337,6 +337,8 @@ class InputProj(nn.Module):
         super().__init__()
         if norm_layer is not None or kernel_size != 3 or stride != 1 or act_layer is not nn.LeakyReLU:
             raise NotImplementedError("InputProj: only the configuration Uformer builds (model.py:1100)")
+        if in_channel < 1:
+            raise NotImplementedError(f"InputProj: in_channel={in_channel}")
         self.proj = nn.Sequential(nn.Conv2d(in_channel, out_channel, kernel_size=3, stride=stride, padding=kernel_size // 2),
                                   act_layer(inplace=True))
         self.in_channel = in_channel
@@ -356,8 +358,8 @@ class OutputProj(nn.Module):
 
     def __init__(self, in_channel=64, out_channel=3, kernel_size=3, stride=1, norm_layer=None, act_layer=None):
         super().__init__()
-        if norm_layer is not None or act_layer is not None or kernel_size != 3 or stride != 1 or out_channel != 3:
-            raise NotImplementedError("OutputProj: only the configuration Uformer builds (model.py:1101)")
+        if norm_layer is not None or act_layer is not None or kernel_size != 3 or stride != 1 or not 1 <= out_channel <= MAX_IN_CHANS:
+            raise NotImplementedError(f"OutputProj: only the configuration Uformer builds (model.py:1101), out_channel 1..{MAX_IN_CHANS}")
         self.proj = nn.Sequential(nn.Conv2d(in_channel, out_channel, kernel_size=3, stride=stride, padding=kernel_size // 2))
         self.in_channel = in_channel
         self.out_channel = out_channel
@@ -563,6 +565,7 @@ class Uformer(nn.Module):
             raise NotImplementedError("drop_rate / attn_drop_rate are 0 in every reference arch")
         if dowsample is not Downsample or upsample is not Upsample:
             raise NotImplementedError("custom sampler classes are not supported")
+        check_image_chans(dd_in, in_chans)
         self.num_enc_layers = len(depths) // 2
         self.num_dec_layers = len(depths) // 2
         self.embed_dim = embed_dim
@@ -995,11 +998,13 @@ class UNet(nn.Module):
 
 
 def get_arch(arch: str, train_ps: int = 128, dd_in: int = 3, embed_dim: int = 32, compute_dtype=torch.bfloat16,
-             token_projection: str = 'linear', cross_modulator: bool = False) -> nn.Module:
+             token_projection: str = 'linear', cross_modulator: bool = False, in_chans: int = 3) -> nn.Module:
     """utils/model_utils.py:56-81 ``get_arch(opt)`` with the option fields as arguments (``token_projection``: its hard-coded 'linear', or
-    'conv' for the paper's ablation row; ``cross_modulator``: its hard-coded False, or True for the cross-modulator variant, inference only)."""
+    'conv' for the paper's ablation row; ``cross_modulator``: its hard-coded False, or True for the cross-modulator variant, inference only).
+    ``dd_in`` is forwarded exactly where the reference forwards it (Uformer_B alone); ``in_chans`` (not an option of the reference's: its
+    constructor default 3) goes to every Uformer arch."""
     common = dict(win_size=8, token_projection=token_projection, token_mlp='leff', modulator=True, compute_dtype=compute_dtype,
-                  cross_modulator=cross_modulator)
+                  cross_modulator=cross_modulator, in_chans=in_chans)
     if arch == 'Uformer':
         return Uformer(img_size=train_ps, embed_dim=embed_dim, **common)
     if arch == 'Uformer_T':

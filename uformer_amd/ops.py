@@ -719,17 +719,23 @@ def input_proj(img: Tensor, w27: Tensor, bias: Tensor) -> Tensor:
 
 
 def output_proj(x: Tensor, w: Tensor, bias: Tensor, B: int, H: int, W: int, img: Optional[Tensor] = None) -> Tensor:
-    """tokens f32 (B*H*W, C2) -> f32 NCHW (B,3,H,W) (+ img).  OutputProj.forward model.py:828-836, :1305."""
+    """tokens f32 (B*H*W, C2) -> f32 NCHW (B,Cout,H,W) (+ img of the same shape); ``w`` (Cout, 9, C2) from packing.pack_output_proj, Cout 1..4.
+    OutputProj.forward model.py:828-836, :1305."""
     _dev(x, w, bias, img)
     x = _c(x, torch.float32)
     C2 = x.shape[-1]
-    out = torch.empty((B, 3, H, W), dtype=torch.float32, device=x.device)
+    Cout = w.shape[0]
+    if w.dim() != 3 or tuple(w.shape[1:]) != (9, C2) or bias.numel() != Cout:
+        raise UformerHipError(f"output_proj: w {tuple(w.shape)} / bias {tuple(bias.shape)} do not match (Cout, 9, {C2}) / (Cout,)")
     if img is not None:
         img = _c(img, torch.float32)
+        if tuple(img.shape) != (B, Cout, H, W):
+            raise UformerHipError(f"output_proj: img {tuple(img.shape)} must have the output's shape {(B, Cout, H, W)}")
+    out = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.check(_lib.load().uf_output_proj_fwd(_ptr(x), C2, _ptr(_c(w, torch.float32)), _ptr(_c(bias, torch.float32)),
-                                                  _ptr(img), _ptr(out), B, H, W, C2, int(img is not None), _stream()),
-                   "uf_output_proj_fwd")
+        _lib.check(_lib.load().uf_output_proj_c_fwd(_ptr(x), C2, _ptr(_c(w, torch.float32)), _ptr(_c(bias, torch.float32)),
+                                                    _ptr(img), _ptr(out), B, H, W, C2, Cout, int(img is not None), _stream()),
+                   "uf_output_proj_c_fwd")
     return out
 
 
@@ -914,19 +920,21 @@ def crop_clamp_canvas(canvas: Tensor, h: int, w: int, clamp: bool = True) -> Ten
 
 
 def crop_augment(frames: Tensor, meta: Tensor, ps: int, hwc: bool = False) -> Tensor:
-    """frames: (N,3,H,W) or (N,H,W,3) (hwc) uint8 / f32 on the GPU; meta int32 (B,4) = [frame index, r0, c0, transform 0..7]
-    -> (B,3,ps,ps) f32 patches (dataset/dataset_denoise.py:54-70; uint8 is divided by 255 like load_img)."""
+    """frames: (N,C,H,W) or (N,H,W,C) (hwc) uint8 / f32 on the GPU, any channel count C; meta int32 (B,4) = [frame index, r0, c0, transform 0..7]
+    -> (B,C,ps,ps) f32 patches (dataset/dataset_denoise.py:54-70; uint8 is divided by 255 like load_img)."""
     _dev(frames, meta)
     if frames.dtype not in (torch.uint8, torch.float32):
         raise UformerHipError("crop_augment: frames must be uint8 or float32")
     frames, meta = _c(frames), _c(meta, torch.int32)
     N = frames.shape[0]
-    H, W = (frames.shape[1], frames.shape[2]) if hwc else (frames.shape[2], frames.shape[3])
+    if frames.dim() != 4:
+        raise UformerHipError(f"crop_augment: frames must be (N,C,H,W) or (N,H,W,C), got {tuple(frames.shape)}")
+    H, W, Cc = (frames.shape[1], frames.shape[2], frames.shape[3]) if hwc else (frames.shape[2], frames.shape[3], frames.shape[1])
     B = meta.shape[0]
-    out = torch.empty((B, 3, ps, ps), dtype=torch.float32, device=frames.device)
+    out = torch.empty((B, Cc, ps, ps), dtype=torch.float32, device=frames.device)
     with torch.cuda.device(frames.device):
-        _lib.check(_lib.load().uf_crop_augment(_ptr(frames), int(frames.dtype == torch.uint8), int(hwc), _ptr(out), _ptr(meta), B, N, H, W, ps,
-                                               _stream()), "uf_crop_augment")
+        _lib.check(_lib.load().uf_crop_augment_c(_ptr(frames), int(frames.dtype == torch.uint8), int(hwc), _ptr(out), _ptr(meta), B, N, Cc, H, W, ps,
+                                                 _stream()), "uf_crop_augment_c")
     return out
 
 
@@ -1063,8 +1071,8 @@ def upsample_cat_bwd(d: Tensor, x: Tensor, w_pk_t: Tensor, B: int, H: int, W: in
 
 def conv3x3_bwd(x: Tensor, dy_rows: Tensor, w: Tensor, B: int, H: int, W: int, nchw: bool = False, act_out: Optional[Tensor] = None, slope: float = 0.01,
                 need_dx: bool = True) -> Tuple[Optional[Tensor], Tensor, Tensor]:
-    """(dx, dW, db) of a 3x3 stride-1 pad-1 Conv2d with <= 4 channels on one side (InputProj / OutputProj): x = f32 token rows
-    (B*H*W, Cin) or the NCHW image when ``nchw``; dy_rows f32 (B*H*W, Cout); ``act_out``: the stored LeakyReLU output rows (InputProj)."""
+    """(dx, dW, db) of a 3x3 stride-1 pad-1 Conv2d with few channels on one side (OutputProj: Cout <= 4; InputProj: Cin <= 8; Cin * Cout * 9 <= 2304):
+    x = f32 token rows (B*H*W, Cin) or the NCHW image when ``nchw``; dy_rows f32 (B*H*W, Cout); ``act_out``: the stored LeakyReLU output rows (InputProj)."""
     _dev(x, dy_rows, w)
     x, dy_rows, w = _c(x, torch.float32), _c(dy_rows, torch.float32), _c(w, torch.float32)
     Cout, Cin = w.shape[0], w.shape[1]

@@ -106,7 +106,7 @@ def pack_input_proj(w: Tensor) -> Tensor:
 
 
 def pack_output_proj(w: Tensor) -> Tensor:
-    """Conv2d weight (3,C2,3,3) -> (3, 9, C2) f32."""
+    """Conv2d weight (CO,C2,3,3) -> (CO, 9, C2) f32, CO = in_chans (1..4)."""
     return w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], 9, w.shape[1]).contiguous().float()
 
 

@@ -99,6 +99,22 @@ class UformerConfig:
         return [(16 * e, 8 * e), (16 * e, 4 * e), (8 * e, 2 * e), (4 * e, e)]
 
 
+MAX_DD_IN = 8        # input planes the stem kernels and their backward take
+MAX_IN_CHANS = 4     # output planes the head kernels and their backward take
+
+
+def check_image_chans(dd_in: int, in_chans: int) -> None:
+    """The image channel counts this project runs.  The reference adds the input to the output exactly when ``dd_in == 3`` (model.py:1305), which
+    needs an output of 3 planes: with ``in_chans`` 2 or 4 its forward raises, with 1 it broadcasts the single plane onto the three by accident."""
+    if dd_in == 3 and in_chans != 3:
+        raise ValueError(f"dd_in={dd_in} adds the input image to the output (global residual, model.py:1305), so in_chans={in_chans} must be 3 as well; "
+                         f"a model without the residual takes any other dd_in")
+    if not (isinstance(dd_in, int) and 1 <= dd_in <= MAX_DD_IN):
+        raise NotImplementedError(f"dd_in={dd_in}: the HIP stem is built for 1..{MAX_DD_IN} input planes")
+    if not (isinstance(in_chans, int) and 1 <= in_chans <= MAX_IN_CHANS):
+        raise NotImplementedError(f"in_chans={in_chans}: the HIP head is built for 1..{MAX_IN_CHANS} output planes")
+
+
 def arch_config(name: str, img_size: int = 256, dd_in: int = 3) -> UformerConfig:
     """kwargs of ``utils.get_arch`` (utils/model_utils.py:65-78); 'tiny' is BASELINE config 0."""
     if name == "Uformer_T":
@@ -282,7 +298,7 @@ def _synth(spec, seed: int) -> Dict[str, torch.Tensor]:
     return out
 
 
-def synth_input(B: int, H: int, W: int, seed: int = 1234) -> torch.Tensor:
-    """U[0,1) images, the range ``load_img`` produces (utils/image_utils.py:31-35)."""
+def synth_input(B: int, H: int, W: int, seed: int = 1234, channels: int = 3) -> torch.Tensor:
+    """U[0,1) images of ``channels`` planes, the range ``load_img`` produces (utils/image_utils.py:31-35)."""
     g = torch.Generator().manual_seed(seed)
-    return torch.rand(B, 3, H, W, generator=g, dtype=torch.float32)
+    return torch.rand(B, channels, H, W, generator=g, dtype=torch.float32)

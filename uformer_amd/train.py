@@ -562,10 +562,11 @@ def _conv_backward(x_src: Tensor, nchw: bool, geom: Tuple[int, int, int, int], w
 def _conv3x3_backward(x: Tensor, nchw: bool, geom: Tuple[int, int, int, int], w: Tensor, dy_rows: Tensor, T: torch.dtype, act_out: Optional[Tensor] = None,
                       need_dx: bool = True) -> Tuple[Optional[Tensor], Tensor, Tensor]:
     """Backward of InputProj / OutputProj (3x3, stride 1, pad 1; LeakyReLU' folded in when ``act_out`` is given): the direct f32
-    kernels for the reference's shapes (embed_dim 16 / 32: a side of <= 4 channels), the patch-matrix route for anything else."""
+    kernels for the reference's shapes (a head of <= 4 planes, a stem of <= 8, weights within 2048 floats), the patch-matrix route for anything
+    else (embed_dim 64 with 4 or more image planes)."""
     B, H, W, Cin = geom
     Cout = w.shape[0]
-    direct = (nchw and Cin <= 4 and Cout in (16, 32, 64)) or (not nchw and Cout <= 4 and Cin % 4 == 0)
+    direct = (nchw and Cin <= 8 and Cout in (16, 32, 64)) or (not nchw and Cout <= 4 and Cin % 4 == 0)
     if direct and Cin * Cout * 9 <= 2048:
         return ops.conv3x3_bwd(x, dy_rows, w, B, H, W, nchw=nchw, act_out=act_out, slope=0.01, need_dx=need_dx)
     if act_out is not None:
@@ -774,7 +775,7 @@ class UformerTape:
             return d.reshape(-1, C)
 
         dy = dy.float()
-        dy_rows = dy.permute(0, 2, 3, 1).reshape(B * H * W, 3)
+        dy_rows = dy.permute(0, 2, 3, 1).reshape(B * H * W, cfg.in_chans)
         C8 = self.head_in.shape[1]
         d, g["output_proj.proj.0.weight"], g["output_proj.proj.0.bias"] = _conv3x3_backward(self.head_in, False, (B, H, W, C8), sd["output_proj.proj.0.weight"], dy_rows, T)
         done(["output_proj.proj.0.weight", "output_proj.proj.0.bias"])
@@ -814,7 +815,7 @@ class UformerTape:
 
 def uformer_forward_backward(img: Tensor, sd: Dict[str, Tensor], dy: Tensor, *, cfg, dtype: torch.dtype = torch.float32,
                              drop_scales: Optional[Tensor] = None, recompute: Optional[bool] = None, loss_scale: float = 1.0) -> Tuple[Tensor, Tensor, Grads]:
-    """Whole-model forward + backward.  img, dy: (B,3,H,W) f32 on the GPU; sd: the reference state_dict on the GPU; cfg:
+    """Whole-model forward + backward.  img (B,dd_in,H,W), dy (B,in_chans,H,W): f32 on the GPU; sd: the reference state_dict on the GPU; cfg:
     uformer_amd.spec.UformerConfig.  Returns (y, d img, parameter gradients keyed like named_parameters()).
     ``loss_scale`` (float16 operands): the reverse sweep runs on ``dy * loss_scale`` and the results are divided by it, what
     torch.cuda.amp.GradScaler does around the reference's backward (train/train_denoise.py:180-184): activation gradients travel as
