@@ -495,8 +495,9 @@ __global__ __launch_bounds__(256) void output_proj_kernel(const float* __restric
             for (int c = 0; c < CO; ++c) wk[ky][c] = *reinterpret_cast<const f32x4*>(ws + (c * 9 + ky * 3 + kx) * C2);
 #pragma unroll
         for (int hr = 0; hr < OP_R + 2; ++hr) {
-            // zero padding by a 0/1 factor, loads unconditional from clamped addresses, 32-bit element offsets
-            const f32x4 v = (my[hr] * mxk) * *reinterpret_cast<const f32x4*>(xs + (size_t)(unsigned)((ro[hr] + ix) * ld_x));
+            // zero padding by a 0/1 factor, loads unconditional from clamped addresses, 32-bit element offsets: the product is UNSIGNED (the
+            // launcher admits up to 2^32 - 2 elements; as a signed product it overflowed from 2^31 elements on, which is undefined)
+            const f32x4 v = (my[hr] * mxk) * *reinterpret_cast<const f32x4*>(xs + (size_t)((unsigned)(ro[hr] + ix) * (unsigned)ld_x));
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky) {
                 const int r = hr - ky;

@@ -150,7 +150,8 @@ __global__ __launch_bounds__((PW * NPG + NC) * 64, WPS) void leff2_kernel(const 
         const unsigned lds_dummy = lds0 + NBUF * BUFB + 2 * AT_BYTES;
         // buffer descriptor over ONE image of h1 (raw, 32-bit offsets, out-of-range lanes read 0 = the conv's zero padding) and this lane's source
         // offset in each of the wave's DMA slots (slot s covers instruction wave + s*NP of the interval): both follow the tile the ISSUE stream is in
-        u32x4 rsrc = {0u, 0u, (unsigned)__builtin_amdgcn_readfirstlane(p.H * p.W * HID * SZ), 0x00020000u};
+        // (unsigned products: one image may hold up to 0xffffff00 bytes, past what a signed 32-bit product may reach)
+        u32x4 rsrc = {0u, 0u, (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(p.H * p.W) * (unsigned)(HID * SZ))), 0x00020000u};
         unsigned voff[NS];
         int issue_k = -1;
         auto set_issue_tile = [&](int k) {
@@ -171,7 +172,7 @@ __global__ __launch_bounds__((PW * NPG + NC) * 64, WPS) void leff2_kernel(const 
                     // MFMA stencil: slot `part` of a halo pixel holds its 16-byte piece part ^ (hx & 6) -- the placement that makes the B-fragment
                     // reads (16 lanes = 16 pixels at a 128-byte stride) conflict-free; a lane fetches the piece that belongs where it lands
                     const int piece = MC ? (part ^ (hx & 6)) : part;
-                    if (hp < HT && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) voff[s] = (unsigned)(((iy * p.W + ix) * HID + g * KCW) * SZ + piece * 16);
+                    if (hp < HT && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) voff[s] = ((unsigned)(iy * p.W + ix) * (unsigned)HID + (unsigned)(g * KCW)) * (unsigned)SZ + (unsigned)(piece * 16);
                 }
             }
             issue_k = k;
