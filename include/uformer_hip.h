@@ -491,7 +491,9 @@ int uf_charbonnier_fwd_bwd(const float* y, const float* target, float* dy, float
  * params / grads / exp_avg / exp_avg_sq / numel are HOST arrays of device pointers / element counts; state is f32.  `step`
  * counts from 1 (bias correction); gradients are multiplied by grad_scale first (1 / world_size folds the all-reduce average).
  *   p *= 1 - lr*wd;  m = lerp(m, g, 1-b1);  v = b2 v + (1-b2) g^2;  p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
- * (hyper-parameters are doubles and the derived scalars are rounded to f32 once, exactly as torch rounds its Python scalars) */
+ * (hyper-parameters are doubles and the derived scalars are rounded to f32 once, exactly as torch rounds its Python scalars).
+ * Each element is updated by one fixed sequence of float32 operations (the lerp is one fma, nothing else is fused): the result does not
+ * depend on the alignment of the four pointers or on the element's position in its tensor. */
 int uf_adamw_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                   const long long* numel, int n_tensors, double lr, double beta1, double beta2, double eps, double weight_decay,
                   int step, double grad_scale, void* stream);
@@ -504,7 +506,8 @@ int uf_adamw_step(float* const* params, const float* const* grads, float* const*
  *   uf_adamw_step_scaled   uf_adamw_step with gradients x grad_scale x state[1], NOTHING written when state[2] != 0, and the bias corrections taken
  *                          at step state[4] + 1 -- a skipped step does not advance the optimizer, as GradScaler.step never calls optimizer.step then
  *   uf_grad_scaler_update  GradScaler.update(): overflow -> scale *= backoff_factor, tracker = 0; else state[4] += 1 and after growth_interval clean
- *                          steps in a row scale *= growth_factor; refreshes 1 / scale and clears found_inf.  No host synchronisation anywhere. */
+ *                          steps in a row scale *= growth_factor; refreshes 1 / scale and clears found_inf.  No host synchronisation anywhere.
+ * state[4] is a float: it stops advancing at 2^24 steps taken (where both bias corrections have long been 1). */
 int uf_grad_scaler_check(const float* const* grads, const long long* numel, int n_tensors, float* scaler_state, void* stream);
 int uf_adamw_step_scaled(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                          const long long* numel, int n_tensors, double lr, double beta1, double beta2, double eps, double weight_decay,
@@ -513,11 +516,13 @@ int uf_grad_scaler_update(float* scaler_state, double growth_factor, double back
 
 /* ---- f-3: evaluation metrics on the device ------------------------------------------------------------------------
  * per-image mean squared difference of (optionally [0,1]-clamped) images: myPSNR = 20 log10(1 / sqrt(mse)) and batch_PSNR
- * (utils/image_utils.py:40-51) follow from it without copying an image to the host.  a, b: f32 (n_images, C, H, W). */
+ * (utils/image_utils.py:40-51) follow from it without copying an image to the host.  a, b: f32 (n_images, C, H, W).
+ * The clamp is torch.clamp's: a NaN pixel stays NaN and makes its image's value NaN. */
 size_t uf_image_metric_workspace_bytes(int n_images, int C, int H, int W);
 int uf_batch_mse(const float* a, const float* b, float* mse_per_image, int n_images, int C, int H, int W, int clamp01,
                  void* ws, size_t ws_bytes, void* stream);
-/* calculate_ssim (utils/caculate_psnr_ssim.py:35-81): images quantised to uint8 levels (x255, round, clamp), 11x11 Gaussian
+/* calculate_ssim (utils/caculate_psnr_ssim.py:35-81): images quantised to uint8 levels (x255, round, low 8 bits: values outside [0,1] wrap as
+ * the reference's uint8 conversion does; NaN, inf and |255 v| >= 2^31 quantise to 0), 11x11 Gaussian
  * sigma 1.5, "valid" region, mean over the map and over channels; one value per image.  H, W > 10. */
 int uf_batch_ssim(const float* a, const float* b, float* ssim_per_image, int n_images, int C, int H, int W, void* ws,
                   size_t ws_bytes, void* stream);
@@ -525,7 +530,7 @@ int uf_batch_ssim(const float* a, const float* b, float* ssim_per_image, int n_i
 /* ---- f-1: arbitrary-resolution wrapper of the evaluation scripts ----------------------------------------------------
  * expand2square (test/test_sidd.py:79-92): canvas f32 (B,C,X,X) = 0 with the (B,C,h,w) image at ((X-h)/2, (X-w)/2); mask
  * (B,1,X,X) = 1 over the image (may be NULL).  One pass, no memset.  uf_crop_clamp is the way back (masked_select + clamp,
- * test/test_sidd.py:108-109). */
+ * test/test_sidd.py:108-109); with clamp01 it is torch.clamp(., 0, 1): NaN stays NaN. */
 int uf_expand2square(const float* img, float* canvas, float* mask, int B, int C, int h, int w, int X, void* stream);
 int uf_crop_clamp(const float* canvas, float* out, int B, int C, int h, int w, int X, int clamp01, void* stream);
 /* The same on a rectangular canvas (B,C,Xh,Xw), Xh >= h and Xw >= w: the image at ((Xh-h)/2, (Xw-w)/2), the placement rule of
@@ -545,7 +550,8 @@ int uf_crop_augment(const void* src, int src_is_u8, int src_hwc, float* out, con
  * Call it with the same meta for an input of dd_in channels and its target of in_chans.  uf_crop_augment is its C = 3 case. */
 int uf_crop_augment_c(const void* src, int src_is_u8, int src_hwc, float* out, const int* meta, int B, int N, int C, int H, int W,
                       int ps, void* stream);
-/* MixUp_AUG.aug (utils/dataset_utils.py:37-53): out[b] = lam[b] x[b] + (1 - lam[b]) x[perm[b]]; out must not alias x. */
+/* MixUp_AUG.aug (utils/dataset_utils.py:37-53): out[b] = lam[b] x[b] + (1 - lam[b]) x[perm[b]]; out must not alias x.  perm (int32, on the
+ * device) is clamped into [0, B), as uf_crop_augment clamps its metadata. */
 int uf_mixup(const float* x, float* out, const float* lam, const int* perm, int B, long long per_sample, void* stream);
 
 /* ---- cross-modulator attention of a decoder block (LeWinTransformerBlock(cross_modulator=True), model.py:873-877, :945-949; Attention :549-595;

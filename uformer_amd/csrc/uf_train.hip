@@ -28,32 +28,44 @@ __device__ __forceinline__ double block_sum(double v, double* sh) {
     return t;   // valid in thread 0
 }
 
+// torch.clamp(v, 0, 1): NaN stays NaN (fminf(fmaxf(v, 0), 1) returns the non-NaN operand: a diverged restoration would score a finite PSNR)
+__device__ __forceinline__ float clamp01_keep_nan(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }
+
 // ---- Charbonnier ------------------------------------------------------------------------------------------------------
 // loss = mean(sqrt(d^2 + eps^2)), d = y - target; dy = gscale * d / sqrt(d^2 + eps^2) / n       (losses.py:47-52)
 __global__ __launch_bounds__(RB) void charbonnier_kernel(const float* __restrict__ y, const float* __restrict__ tgt, float* __restrict__ dy,
                                                          double* __restrict__ partial, long long n4, long long n, float eps2, float gs) {
+    // every float operation below is one IEEE operation, never a contracted fma: the 4-wide body and the tail give the same bits for the same values
+#pragma clang fp contract(off)
     __shared__ double sh[RB / 64];
+    // The loss term is taken in double from the float32 inputs (y - target is exact there): the reported mean is the correctly rounded float64 mean to
+    // within its last bit.  The float32 r of the gradient carries three roundings (d * d, + eps^2, sqrt); summed as it was, a loss over a handful of
+    // elements missed the float64 value by more than a float32 ulp.  The f64 sqrt costs: 18.8 us against 16.6 us for this kernel + finalize at
+    // 32 x 3 x 256 x 256 elements on an MI355X (4.0 against 4.5 TB/s), once per training step of 62 ms.
+    auto term = [eps2](float yy, float tt) {
+#pragma clang fp contract(off)
+        const double dd = (double)yy - (double)tt;
+        return sqrt(dd * dd + (double)eps2);
+    };
     double acc = 0.0;
     const long long stride = (long long)gridDim.x * RB;
     for (long long i = (long long)blockIdx.x * RB + threadIdx.x; i < n4; i += stride) {
         const f32x4 a = reinterpret_cast<const f32x4*>(y)[i], b = reinterpret_cast<const f32x4*>(tgt)[i];
         f32x4 g;
-        float s = 0.f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float d = a[k] - b[k];
             const float r = sqrtf(d * d + eps2);
-            s += r;
+            acc += term(a[k], b[k]);
             g[k] = gs * d / r;
         }
-        acc += (double)s;
         if (dy) reinterpret_cast<f32x4*>(dy)[i] = g;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)       // tail (n % 4 elements), at most 3
         for (long long i = n4 * 4; i < n; ++i) {
             const float d = y[i] - tgt[i];
             const float r = sqrtf(d * d + eps2);
-            acc += (double)r;
+            acc += term(y[i], tgt[i]);
             if (dy) dy[i] = gs * d / r;
         }
     const double t = block_sum(acc, sh);
@@ -102,10 +114,14 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamWArgs a) {
         stepf = (float)(a.lr / (1.0 - pow(a.beta1, t)));
         bc2s = (float)sqrt(1.0 - pow(a.beta2, t));
     }
+    // a fixed sequence of single IEEE operations (nothing is contracted by the compiler): the 128-bit path, the scalar path of unaligned tensors (gradients that are views
+    // into a flat all-reduce bucket) and the n % 4 tail round a weight the same way, wherever its operands sit in memory
     auto upd = [&](float& pp, float gg, float& mm, float& vv) {
+#pragma clang fp contract(off)
         gg *= gs;
         pp *= a.decay;
-        mm = mm + a.omb1 * (gg - mm);
+        mm = fmaf(a.omb1, gg - mm, mm);                 // ONE fused operation, spelled out: where m and g cancel, torch's lerp (an fma too) is only matched by it;
+                                                        // every other line rounds each product and sum on its own
         vv = vv * a.b2 + a.omb2 * (gg * gg);
         pp -= stepf * (mm / (sqrtf(vv) / bc2s + a.eps));
     };
@@ -145,7 +161,7 @@ __global__ __launch_bounds__(RB) void sqdiff_kernel(const float* __restrict__ a,
     double acc = 0.0;
     for (long long i = (long long)blk * RB + threadIdx.x; i < per_img; i += (long long)blocks_per_img * RB) {
         float x = pa[i], y = pb[i];
-        if (clamp01) { x = fminf(fmaxf(x, 0.f), 1.f); y = fminf(fmaxf(y, 0.f), 1.f); }
+        if (clamp01) { x = clamp01_keep_nan(x); y = clamp01_keep_nan(y); }
         const float d = x - y;
         acc += (double)(d * d);
     }
@@ -236,7 +252,7 @@ __global__ __launch_bounds__(256) void crop_clamp_kernel(const float* __restrict
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const int xx = (int)(i % w), yy = (int)((i / w) % h), pc = (int)(i / ((long long)w * h));
         float v = canvas[((size_t)pc * Xh + y0 + yy) * Xw + x0 + xx];
-        if (clamp01) v = fminf(fmaxf(v, 0.f), 1.f);
+        if (clamp01) v = clamp01_keep_nan(v);
         out[i] = v;
     }
 }
@@ -279,12 +295,15 @@ __global__ __launch_bounds__(256) void crop_aug_kernel(const S* __restrict__ src
 // MixUp (utils/dataset_utils.py:44-53): out[b] = lam[b] * x[b] + (1 - lam[b]) * x[perm[b]]
 __global__ __launch_bounds__(256) void mixup_kernel(const float* __restrict__ x, float* __restrict__ out, const float* __restrict__ lam, const int* __restrict__ perm,
                                                     int B, long long per) {
+#pragma clang fp contract(off)
     const long long n = (long long)B * per;
     for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long long)gridDim.x * 256) {
         const int b = (int)(t / per);
         const long long r = t - (long long)b * per;
         const float l = lam[b];
-        out[t] = l * x[t] + (1.0f - l) * x[(size_t)perm[b] * per + r];
+        int pb = perm[b];                            // device-side index, clamped into the batch like crop_aug_kernel's metadata
+        pb = pb < 0 ? 0 : (pb >= B ? B - 1 : pb);
+        out[t] = l * x[t] + (1.0f - l) * x[(size_t)pb * per + r];
     }
 }
 
@@ -311,7 +330,7 @@ extern "C" int uf_charbonnier_fwd_bwd(const float* y, const float* target, float
     UF_REQUIRE(ws_bytes >= (size_t)nb * sizeof(double), UF_ERR_WORKSPACE, "uf_charbonnier_fwd_bwd: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     {
-        ScopedTimer tm("charbonnier", 6.0 * n, (dy ? 12.0 : 8.0) * n, st);
+        ScopedTimer tm("charbonnier", 11.0 * n, (dy ? 12.0 : 8.0) * n, st);      // 6 f32 operations for dy + 5 f64 for the loss term
         hipLaunchKernelGGL(charbonnier_kernel, dim3(nb), dim3(RB), 0, st, y, target, dy, (double*)ws, n / 4, n, eps * eps, grad_scale / (float)n);
     }
     hipLaunchKernelGGL(finalize_mean_kernel, dim3(1), dim3(RB), 0, st, (const double*)ws, nb, 1.0 / (double)n, loss);
