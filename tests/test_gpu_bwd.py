@@ -769,15 +769,22 @@ def test_layernorm_bwd_cast_is_the_fork_of_its_dx(dtype, C, ln_windowed, cast_wi
         assert not torch.equal(cast.float(), torch.zeros_like(cast.float()))
 
 
-def test_block_backward_with_and_without_the_fused_fork(monkeypatch):
+@pytest.mark.parametrize("geometry", ["win8_leff", "win4_bottleneck", "win8_mlp"])
+def test_block_backward_with_and_without_the_fused_fork(monkeypatch, geometry):
     """The stored-intermediates backward of a stage of blocks with the operand copies written by the LayerNorm backward kernels against the
     same backward with separate uf_grad_fork passes: the fused kernel adds the residual gradient with one fma, so dx1 differs in the last f32
-    bit here and there and a bf16 operand made from it by one ulp -- everything agrees to bf16 rounding."""
+    bit here and there and a bf16 operand made from it by one ulp -- everything agrees to bf16 rounding.  Over the three geometries of the one
+    attention half: tiny32 at 128^2 (8x8 windows, LeFF), tiny32 built for 64x64 patches at 64^2 (a 4x4-window bottleneck), token_mlp='ffn'."""
+    import dataclasses
     from uformer_amd import spec, train
-    cfg = spec.arch_config("tiny32", img_size=128)
+    size = 64 if geometry == "win4_bottleneck" else 128
+    cfg = spec.arch_config("tiny32", img_size=size)
+    if geometry == "win8_mlp":
+        cfg = dataclasses.replace(cfg, token_mlp="ffn")
+    assert cfg.stage_windows()[4] == (4 if geometry == "win4_bottleneck" else 8)
     sd = {k: v.cuda() for k, v in spec.synth_state_dict(cfg, 77).items()}
-    x = spec.synth_input(2, 128, 128, 5).cuda()
-    dy = torch.randn(2, 3, 128, 128, generator=g(140)).cuda() * 1e-3
+    x = spec.synth_input(2, size, size, 5).cuda()
+    dy = torch.randn(2, 3, size, size, generator=g(140)).cuda() * 1e-3
     drop = train.sample_drop_scales([0.3] * sum(cfg.depths), 2, "cuda", generator=torch.Generator(device="cuda").manual_seed(3))
     outs = []
     for fuse in (True, False):
@@ -789,6 +796,43 @@ def test_block_backward_with_and_without_the_fused_fork(monkeypatch):
     assert set(g0) == set(g1)
     worst = max((rel(g0[k], g1[k].cpu()), k) for k in g0 if g1[k].abs().max() > 0)
     assert worst[0] < 2e-2, worst
+
+
+BLOCK_KINDS = {"leff_win8": dict(H=16, C=32, heads=1, shift=4, win=8, modulator=True, token_mlp="leff"),      # the smallest maps where the roll, the per-image
+               "mlp_win8": dict(H=16, C=32, heads=1, shift=4, win=8, modulator=True, token_mlp="ffn"),        # scale and a second window all matter
+               "leff_win4": dict(H=8, C=64, heads=2, shift=0, win=4, modulator=False, token_mlp="leff")}
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("kind", list(BLOCK_KINDS))
+def test_block_backward_third_result_is_the_fork_of_its_dx(monkeypatch, kind, dtype):
+    """lewin_block_backward(sv, dy, next_scale=s) -> (dx, g, cast) for every kind of block the one attention half serves: dx and every gradient
+    bit-identical to the two-result call on the same ``sv``, and ``cast`` bit-identical to uf_grad_fork of that dx (what the block that ran before
+    takes as its ``dyT``); without the fused fork the third result is None.  test_layernorm_bwd_cast_is_the_fork_of_its_dx states the same for
+    the kernel alone."""
+    from uformer_amd import ops, spec, train
+    kd = BLOCK_KINDS[kind]
+    B, H, C, heads = 2, kd["H"], kd["C"], kd["heads"]
+    L, M = H * H, B * H * H
+    p = {k: v.cuda() for k, v in spec._synth(list(spec.block_spec("", C, heads, kd["win"], kd["modulator"], mod_win=8, token_mlp=kd["token_mlp"])), 150).items()}
+    x = torch.randn(B, L, C, generator=g(151)).cuda()
+    dy = torch.randn(B, L, C, generator=g(152)).cuda()
+    drop = torch.tensor([[0.0, 2.0], [2.0, 0.0]]).cuda()                  # each branch dropped for one image, kept (1 / keep = 2) for the other
+    _, sv = train.lewin_block_forward(x, p, "", heads, kd["shift"], dtype, drop, hw=(H, H))
+    assert sv["win"] == kd["win"] and sv["mlp"] == (kd["token_mlp"] == "ffn") and sv["mod"] == kd["modulator"]
+    dx0, g0 = train.lewin_block_backward(sv, dy)
+    assert dx0.abs().max() > 0
+    for next_scale in (torch.tensor([1.25, 0.0]).cuda(), None):
+        dx, gb, cast = train.lewin_block_backward(sv, dy, next_scale=next_scale)
+        assert torch.equal(dx, dx0)
+        assert set(gb) == set(g0)
+        for k in g0:
+            assert torch.equal(gb[k], g0[k]), k
+        ref = ops.grad_fork(dx.reshape(M, C), None, next_scale, B, H, H, dtype)[1]
+        assert cast.dtype == dtype and torch.equal(cast, ref)
+    monkeypatch.setattr(train, "_FUSE_FORK", False)
+    out = train.lewin_block_backward(sv, dy, next_scale=torch.tensor([1.25, 0.0]).cuda())
+    assert len(out) == 3 and out[2] is None
 
 
 @pytest.mark.parametrize("dtype", MODES)

@@ -241,3 +241,35 @@ def test_no_compile_time_switches_in_csrc():
     hits = [f"{os.path.basename(f)}:{n}: {line.rstrip()}" for f in files for n, line in enumerate(open(f), 1) if switch.search(line)]
     assert not hits, ("compile-time experiment switches in uformer_amd/csrc -- keep the experiment in an A/B copy (scripts/build_variant.sh) "
                       "and land only the winner:\n" + "\n".join(hits))
+
+
+def test_block_form_is_the_table_the_tape_used_inline(monkeypatch):
+    """train.block_form against the expressions UformerTape.forward evaluated inline before it existed, over every recompute choice, operand
+    type, width / head count, window, feed-forward kind and packing switch; the two recompute forms never both apply."""
+    import itertools
+    from uformer_amd import train
+    widths = [(16, 1), (32, 1), (64, 2), (64, 1), (256, 8), (256, 4), (512, 16), (1024, 16)]
+    seen = set()
+    for native_pack in (True, False):
+        monkeypatch.setattr(train, "_NATIVE_PACK", native_pack)
+        for recompute, T, (C, heads), win, is_mlp in itertools.product((False, True), (torch.float32, torch.bfloat16, torch.float16), widths, (4, 8),
+                                                                       (False, True)):
+            fusable = recompute and C == 32 * heads and win == 8 and not is_mlp
+            native = C % 32 == 0 and C % heads == 0 and native_pack and win == 8 and not is_mlp
+            if win == 4 and C % 32 == 0 and native_pack and not is_mlp:
+                pack = "native4"
+            elif native:
+                pack = "native"
+            else:
+                pack = ("aten", fusable or train.fused_attn_covers(T, C, heads))
+            unfused_rc = recompute and win == 8 and (C == 64 * heads or (is_mlp and C == 32 * heads))
+            assert not (unfused_rc and fusable)
+            run = "recompute_unfused" if unfused_rc else "recompute_fused" if fusable else "kept"
+            got = train.block_form(recompute, T, C, heads, win, is_mlp)
+            assert got == (pack, run), (native_pack, recompute, T, C, heads, win, is_mlp, got)
+            if pack not in ("native", "native4"):
+                assert isinstance(got[0][1], bool)
+            seen.add((pack if isinstance(pack, str) else pack[0], run))
+    # every row of the table is reached (a 4x4-window block never recomputes)
+    assert seen == {(p, r) for p in ("native", "native4", "aten") for r in ("kept", "recompute_fused", "recompute_unfused")} - {
+        ("native4", "recompute_fused"), ("native4", "recompute_unfused")}

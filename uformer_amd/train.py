@@ -290,34 +290,30 @@ def lewin_block_forward(x: Tensor, p: Dict[str, Tensor], prefix: str, heads: int
         # x + DropPath(window_reverse(proj(o))): the residual add, the scale and the un-partition in the projection GEMM's store   model.py:975-986
         x1 = ops.linear_residual(o, pk.wp, f("attn.proj.bias"), x2, s1, B, H, W, windowed=True, shift=shift)
         z = ops.layernorm(x1, f("norm2.weight"), f("norm2.bias"), B=B, H=H, W=W, dtype=T)
-    if block_is_mlp(p, prefix):
+    mlp = block_is_mlp(p, prefix)
+    h1 = c = g2 = None
+    if mlp:
         # Mlp: y = x1 + DropPath(fc2(GELU(fc1(z)))) (model.py:636-642, :987).  Only the pre-activation a1 is kept: the backward recomputes
         # T(GELU(a1)) for fc2's weight gradient in one elementwise pass (uf_gelu_fwd) instead of storing 4C more channels per token.
         if win == 4:
             raise NotImplementedError("token_mlp='ffn' is not built for 4x4-window blocks")
         if not fused_attn:
             a1 = ops.linear(z, pk.w1, f("mlp.fc1.bias"))
-        y = None
-        if need_y:
-            y = ops.linear_residual(ops.gelu(a1), pk.w2, f("mlp.fc2.bias"), x1, s2, B, H, W).reshape(B, L, C)
-        saved = dict(s1=s1, s2=s2, p=p, prefix=prefix, heads=heads, shift=shift, T=T, shape=(B, L, C), hw=(H, W), x2=x2, xn=xn, q=q, k=k, vt=vt, o=o, x1=x1, z=z, a1=a1,
-                     h1=None, c=None, g2=None, pk=pk, mod=pk.mod is not None, win=win, qkv=qkv, mlp=True)
-        return y, saved
-    if fused_attn or _GELU_IN:     # linear1 keeps only its pre-activation (the backward needs that one); the stencil activates it as it loads it
-        if not fused_attn:
-            a1 = ops.linear(z, pk.w1, f("mlp.linear1.0.bias"))
-        h1 = None
-        c, g2 = ops.dwconv3x3_pre_gelu(a1.reshape(B, H, W, 4 * C), pk.w9, f("mlp.dwconv.0.bias"), gelu_in=True)
     else:
-        a1, h1 = ops.linear_pre_gelu(z, pk.w1, f("mlp.linear1.0.bias"))      # pre-activation (kept for GELU') and activation, one pass
-        h1 = h1.reshape(B, H, W, 4 * C)
-        c, g2 = ops.dwconv3x3_pre_gelu(h1, pk.w9, f("mlp.dwconv.0.bias"))    # likewise for the stencil and the second GELU
-    g2 = g2.reshape(M, 4 * C)
+        if fused_attn or _GELU_IN:  # linear1 keeps only its pre-activation (the backward needs that one); the stencil activates it as it loads it
+            if not fused_attn:
+                a1 = ops.linear(z, pk.w1, f("mlp.linear1.0.bias"))
+            c, g2 = ops.dwconv3x3_pre_gelu(a1.reshape(B, H, W, 4 * C), pk.w9, f("mlp.dwconv.0.bias"), gelu_in=True)
+        else:
+            a1, h1 = ops.linear_pre_gelu(z, pk.w1, f("mlp.linear1.0.bias"))      # pre-activation (kept for GELU') and activation, one pass
+            h1 = h1.reshape(B, H, W, 4 * C)
+            c, g2 = ops.dwconv3x3_pre_gelu(h1, pk.w9, f("mlp.dwconv.0.bias"))    # likewise for the stencil and the second GELU
+        g2 = g2.reshape(M, 4 * C)
     y = None
-    if need_y:
-        y = ops.linear_residual(g2, pk.w2, f("mlp.linear2.0.bias"), x1, s2, B, H, W).reshape(B, L, C)     # x1 + DropPath(linear2(.))   model.py:987
+    if need_y:                     # x1 + DropPath(linear2(.) / fc2(.))   model.py:987
+        y = ops.linear_residual(ops.gelu(a1) if mlp else g2, pk.w2, f("mlp.fc2.bias" if mlp else "mlp.linear2.0.bias"), x1, s2, B, H, W).reshape(B, L, C)
     saved = dict(s1=s1, s2=s2, p=p, prefix=prefix, heads=heads, shift=shift, T=T, shape=(B, L, C), hw=(H, W), x2=x2, xn=xn, q=q, k=k, vt=vt, o=o, x1=x1, z=z, a1=a1,
-                 h1=h1, c=c, g2=g2, pk=pk, mod=pk.mod is not None, win=win, qkv=qkv)
+                 h1=h1, c=c, g2=g2, pk=pk, mod=pk.mod is not None, win=win, qkv=qkv, mlp=mlp)
     return y, saved
 
 
@@ -337,15 +333,37 @@ _VERBOSE = False           # True: say which training form (kept-intermediates /
 _NATIVE_PACK = True        # False: per-step operand packing through ATen (BlockPack) instead of uf_pack_block_train
 
 
+def block_form(recompute: bool, T: torch.dtype, C: int, heads: int, win: int, is_mlp: bool):
+    """The form one block takes in the training tape -> (pack, run).  ``pack``, who makes the per-step operands:
+      "native"         uf_pack_block_train (5 launches; its pack also serves the op-by-op form as tensor views): an 8x8-window LeFF block, C % 32 == 0
+      "native4"        native_block4_pack: a 4x4-window LeFF block (the bottleneck of a model built for 64x64 patches), C % 32 == 0
+      ("aten", fused)  BlockPack(fused=fused): everything else -- an Mlp block (token_mlp 'ffn': no native pack), C % 32 != 0 (Uformer_T), _NATIVE_PACK off
+    ``run``, what the block keeps for its backward:
+      "recompute_fused"    its input; the fused kernels forward, the block-level C backward: recompute, 8x8 window, LeFF, head_dim 32
+      "recompute_unfused"  its input; the backward reruns the op-by-op forward (need_y=False: up to the stencil) and differentiates it, the same kernels
+                           on the same operands as the kept form: recompute, 8x8 window, head_dim 64, or an Mlp block (no block-level C backward) of head_dim 32
+      "kept"               every intermediate of the op-by-op forward: everything else -- head_dim 16 and 4x4-window blocks in both training forms"""
+    fusable = bool(recompute) and C == 32 * heads and win == 8 and not is_mlp
+    unfused_rc = bool(recompute) and win == 8 and (C == 64 * heads or (is_mlp and C == 32 * heads))
+    run = "recompute_unfused" if unfused_rc else "recompute_fused" if fusable else "kept"
+    if win == 4 and C % 32 == 0 and _NATIVE_PACK and not is_mlp:
+        return "native4", run
+    if C % 32 == 0 and C % heads == 0 and _NATIVE_PACK and win == 8 and not is_mlp:
+        return "native", run
+    return ("aten", fusable or fused_attn_covers(T, C, heads)), run
+
+
 class _Side:
     """Weight-gradient jobs of a block on a side stream (nothing downstream in the block reads them), as the C++ block backward does
     (UF_BWD_STREAMS=1 turns it off): ``run(fn)`` orders the side stream behind everything enqueued on the caller's stream so far and runs
     ``fn`` on it; ``join()`` makes the caller's stream wait for the side stream.  Allocations made inside ``run`` belong to the side
-    stream; inputs stay referenced by the caller until after ``join()``, so the caching allocator cannot hand them out early."""
+    stream; a job (with the inputs its closure names) stays referenced here until ``join()``, so the caching allocator cannot hand an input
+    out early when the half of the backward that made it has returned."""
 
     def __init__(self, device):
         n = int(os.environ.get("UF_BWD_STREAMS", "2"))           # 1: off;  2: one side stream;  3+: jobs alternate over n - 1 side streams
         self.on = n > 1
+        self.jobs = []
         if self.on:
             key = str(device)
             have = _SIDE_STREAMS.setdefault(key, [])
@@ -358,6 +376,7 @@ class _Side:
             return fn()
         side = self.sides[self.k % len(self.sides)]
         self.k += 1
+        self.jobs.append(fn)
         side.wait_stream(self.cur)
         with torch.cuda.stream(side):
             return fn()
@@ -366,6 +385,7 @@ class _Side:
         if self.on:
             for side in self.sides:
                 self.cur.wait_stream(side)
+        self.jobs.clear()
 
 
 _FUSE_FORK = True          # False: separate grad_fork passes (tests set the attribute)
@@ -376,22 +396,26 @@ def lewin_block_backward(sv: Saved, dy: Tensor, dyT: Optional[Tensor] = None, ne
     """dy: (B, L, C) gradient of the block output -> (dx, gradients keyed like the reference's named_parameters()).
     ``dyT``: T(dy * s2) if the caller already has it (the LayerNorm backward of the block that ran AFTER this one wrote it next to its dx).
     ``next_scale`` (the LeFF DropPath scales (B,) of the block that ran BEFORE this one, or None for no scaling): also return
-    T(dx * next_scale) as a third result -- that block's ``dyT``."""
-    p, prefix, heads, shift, T = sv["p"], sv["prefix"], sv["heads"], sv["shift"], sv["T"]
-    side = _Side(dy.device)
+    T(dx * next_scale) as a third result -- that block's ``dyT``.
+    The sum of two halves: the feed-forward half (_leff_backward or _mlp_backward) and _attn_half_backward."""
     B, L, C = sv["shape"]
-    H, W = sv["hw"] if "hw" in sv else block_hw(L, None)
-    M, hd = B * L, C // heads
-    f = lambda k: p[prefix + k]                                             # noqa: E731
+    H, W = sv["hw"]
+    side = _Side(dy.device)
     g: Grads = {}
-    dyf = dy.reshape(M, C).float()
+    dyf = dy.reshape(B * L, C).float()
     if dyT is None:
-        _, dyT = ops.grad_fork(dyf, None, sv["s2"], B, H, W, T)              # gradient entering the (scaled) LeFF branch, as a GEMM operand
-    if sv.get("mlp"):
-        return _mlp_block_backward(sv, dyf, dyT, next_scale, side, g)
-    # LeFF: linear2 -> GELU -> depthwise -> GELU -> linear1                                   (model.py:666-685)
+        _, dyT = ops.grad_fork(dyf, None, sv["s2"], B, H, W, sv["T"])        # gradient entering the (scaled) LeFF branch, as a GEMM operand
+    dz = (_mlp_backward if sv["mlp"] else _leff_backward)(sv, dyT, side, g)
+    return _attn_half_backward(sv, dz, dyf, next_scale, side, g)
+
+
+def _leff_backward(sv: Saved, dyT: Tensor, side: "_Side", g: Grads) -> Tensor:
+    """LeFF backward, linear2 -> GELU -> depthwise -> GELU -> linear1 (model.py:666-685): fills ``g``, returns dz (the gradient entering LN2)."""
+    prefix, pk = sv["prefix"], sv["pk"]
+    B, L, C = sv["shape"]
+    H, W = sv["hw"]
+    M = B * L
     g[prefix + "mlp.linear2.0.weight"], g[prefix + "mlp.linear2.0.bias"] = side.run(lambda: ops.linear_wgrad(dyT, sv["g2"]))
-    pk: BlockPack = sv["pk"]
     dc = ops.linear_mul_dgelu(dyT, pk.w2_t, _zeros(4 * C, dyT.device), sv["c"].reshape(M, 4 * C)).reshape(B, H, W, 4 * C)   # dY W2, times GELU'(c)
     if _DW_BWD_FUSED:      # flipped-tap stencil times GELU'(a1) AND the tap / bias gradients, one pass over dc (h1 recomputed from a1)
         da1, dw9, g[prefix + "mlp.dwconv.0.bias"] = ops.dwconv3x3_bwd(dc, pk.w9_flip, sv["a1"].reshape(B, H, W, 4 * C))
@@ -405,106 +429,60 @@ def lewin_block_backward(sv: Saved, dy: Tensor, dyT: Optional[Tensor] = None, ne
         g[prefix + "mlp.dwconv.0.weight"], g[prefix + "mlp.dwconv.0.bias"] = side.run(_dw)
         da1 = ops.dwconv3x3_mul_dgelu(dc, pk.w9_flip, sv["a1"].reshape(B, H, W, 4 * C)).reshape(M, 4 * C)   # flipped-tap stencil, times GELU'(a1)
     g[prefix + "mlp.linear1.0.weight"], g[prefix + "mlp.linear1.0.bias"] = side.run(lambda: ops.linear_wgrad(da1, sv["z"]))
-    dz = _input_grad(da1, pk.w1_t)
-    if sv.get("win", 8) == 4:
-        # 4x4-window block: the attention half on raster rows (no partition, roll or modulator)                    (model.py:951-986)
-        if _FUSE_FORK and dz.dtype == T:
-            dx1, g[prefix + "norm2.weight"], g[prefix + "norm2.bias"], dyw = ops.layernorm_bwd_fused(sv["x1"], f("norm2.weight"), dz, B, H, W, add=dyf,
-                                                                                                     cast=dict(scale=sv["s1"], windowed=False, shift=0))
-        else:
-            dx1, g[prefix + "norm2.weight"], g[prefix + "norm2.bias"] = ops.layernorm_bwd_fused(sv["x1"], f("norm2.weight"), dz, B, H, W)
-            dx1, dyw = ops.grad_fork(dx1, dyf, sv["s1"], B, H, W, T, want_sum=True)
-        g[prefix + "attn.proj.weight"], g[prefix + "attn.proj.bias"] = side.run(lambda: ops.linear_wgrad(dyw, sv["o"]))
-        do = _input_grad(dyw, pk.wp_t)
-        dqkv, dscore = ops.window4_attention_bwd(sv["qkv"], pk.rpb4, do, B, H, W, heads)
-        g[prefix + "attn.relative_position_bias_table"] = side.run(lambda: ops.rpb4_table_grad(dscore))   # fixed-order gather: deterministic
-        dWqkv, dbqkv = side.run(lambda: ops.linear_wgrad(dqkv, sv["xn"]))
-        g[prefix + "attn.qkv.to_q.weight"], g[prefix + "attn.qkv.to_kv.weight"] = dWqkv[:C], dWqkv[C:]
-        g[prefix + "attn.qkv.to_q.bias"], g[prefix + "attn.qkv.to_kv.bias"] = dbqkv[:C], dbqkv[C:]
-        dxn = _input_grad(dqkv, pk.wqkv_t)
-        if next_scale is not _NO_CAST and _FUSE_FORK and dxn.dtype == T:
-            dx, g[prefix + "norm1.weight"], g[prefix + "norm1.bias"], dyT_next = ops.layernorm_bwd_fused(sv["x2"], f("norm1.weight"), dxn, B, H, W, add=dx1,
-                                                                                                         cast=dict(scale=next_scale, windowed=False))
-            side.join()
-            return dx.reshape(B, L, C), g, dyT_next
-        dx, g[prefix + "norm1.weight"], g[prefix + "norm1.bias"] = ops.layernorm_bwd_fused(sv["x2"], f("norm1.weight"), dxn, B, H, W, add=dx1)
-        side.join()
-        if next_scale is not _NO_CAST:
-            return dx.reshape(B, L, C), g, None
-        return dx.reshape(B, L, C), g
-    # attention half: proj -> attention -> qkv -> (+modulator) -> partition/roll -> LN1              (model.py:951-986)
-    # dx1 = LN2-path gradient + dy (the residual), and the (scaled) gradient entering the attention branch in window order
+    return _input_grad(da1, pk.w1_t)
+
+
+def _mlp_backward(sv: Saved, dyT: Tensor, side: "_Side", g: Grads) -> Tensor:
+    """Backward of the reference's Mlp, fc2 -> GELU -> fc1 (model.py:636-642): fills ``g``, returns dz.  Composed from the entry points the LeFF
+    half uses: uf_linear_wgrad and the input-gradient GEMM with the GELU' epilogue (uf_linear_mul_dgelu)."""
+    prefix, pk, C = sv["prefix"], sv["pk"], sv["shape"][2]
+    h = ops.gelu(sv["a1"])                                                  # T(GELU(a1)), recomputed: what fc2 read in the forward
+    g[prefix + "mlp.fc2.weight"], g[prefix + "mlp.fc2.bias"] = side.run(lambda: ops.linear_wgrad(dyT, h))
+    da1 = ops.linear_mul_dgelu(dyT, pk.w2_t, _zeros(4 * C, dyT.device), sv["a1"])       # dY W2, times GELU'(a1)
+    g[prefix + "mlp.fc1.weight"], g[prefix + "mlp.fc1.bias"] = side.run(lambda: ops.linear_wgrad(da1, sv["z"]))
+    return _input_grad(da1, pk.w1_t)
+
+
+def _attn_half_backward(sv: Saved, dz: Tensor, dyf: Tensor, next_scale, side: "_Side", g: Grads):
+    """The attention half of every op-level block backward, proj -> attention -> qkv -> (+modulator) -> partition/roll -> LN1 (model.py:951-986),
+    from ``dz`` (the gradient entering LN2) and ``dyf`` (the f32 gradient of the block output): fills ``g``, joins ``side`` and returns
+    lewin_block_backward's result.  An 8x8-window block works on window rows (partition and roll folded into the LayerNorm backward kernels, q / k /
+    vt saved apart, an optional modulator); a 4x4-window block on raster rows (no partition, roll or modulator; q|k|v saved as one ``qkv``)."""
+    p, prefix, heads, T, pk = sv["p"], sv["prefix"], sv["heads"], sv["T"], sv["pk"]
+    B, L, C = sv["shape"]
+    H, W = sv["hw"]
+    f = lambda k: p[prefix + k]                                             # noqa: E731
+    win8 = sv["win"] == 8
+    rows = dict(windowed=True, shift=sv["shift"]) if win8 else dict(windowed=False, shift=0)     # the order of the attention branch's rows
+    # dx1 = LN2-path gradient + dy (the residual), and the (scaled) gradient entering the attention branch in that order
     if _FUSE_FORK and dz.dtype == T:                                        # both from the LayerNorm backward kernel
         dx1, g[prefix + "norm2.weight"], g[prefix + "norm2.bias"], dyw = ops.layernorm_bwd_fused(sv["x1"], f("norm2.weight"), dz, B, H, W, add=dyf,
-                                                                                                 cast=dict(scale=sv["s1"], windowed=True, shift=shift))
+                                                                                                 cast=dict(scale=sv["s1"], **rows))
     else:
         dx1, g[prefix + "norm2.weight"], g[prefix + "norm2.bias"] = ops.layernorm_bwd_fused(sv["x1"], f("norm2.weight"), dz, B, H, W)
-        dx1, dyw = ops.grad_fork(dx1, dyf, sv["s1"], B, H, W, T, windowed=True, shift=shift, want_sum=True)
+        dx1, dyw = ops.grad_fork(dx1, dyf, sv["s1"], B, H, W, T, want_sum=True, **rows)
     g[prefix + "attn.proj.weight"], g[prefix + "attn.proj.bias"] = side.run(lambda: ops.linear_wgrad(dyw, sv["o"]))
     do = _input_grad(dyw, pk.wp_t)
-    dqkv, dbias = ops.window_attention_bwd_qkv(sv["q"], sv["k"], sv["vt"], pk.bias, do, H, W, shift)    # heads merged, dq times the query scale
-    g[prefix + "attn.relative_position_bias_table"] = side.run(lambda: ops.rpb_table_grad(dbias))   # gather over the pairs of each table entry: deterministic
-    nW = M // 64
+    if win8:               # heads merged, dq times the query scale; the table gradient gathers over the pairs of each entry in a fixed order: deterministic
+        dqkv, dbias = ops.window_attention_bwd_qkv(sv["q"], sv["k"], sv["vt"], pk.bias, do, H, W, rows["shift"])
+        g[prefix + "attn.relative_position_bias_table"] = side.run(lambda: ops.rpb_table_grad(dbias))
+    else:
+        dqkv, dscore = ops.window4_attention_bwd(sv["qkv"], pk.rpb4, do, B, H, W, heads)
+        g[prefix + "attn.relative_position_bias_table"] = side.run(lambda: ops.rpb4_table_grad(dscore))
     dWqkv, dbqkv = side.run(lambda: ops.linear_wgrad(dqkv, sv["xn"]))
     g[prefix + "attn.qkv.to_q.weight"], g[prefix + "attn.qkv.to_kv.weight"] = dWqkv[:C], dWqkv[C:]
     g[prefix + "attn.qkv.to_q.bias"], g[prefix + "attn.qkv.to_kv.bias"] = dbqkv[:C], dbqkv[C:]
     dxn = _input_grad(dqkv, pk.wqkv_t)
     if sv["mod"]:                                                           # the (64, C) table is added to every window
-        g[prefix + "modulator.weight"] = side.run(lambda: ops.rows_sum(dxn.reshape(nW, 64 * C)).reshape(64, C))
-    # LN1 backward reads dxn in window order (window_reverse + roll back folded in) and adds the residual path's gradient
-    if next_scale is not _NO_CAST and _FUSE_FORK and dxn.dtype == T:
-        dx, g[prefix + "norm1.weight"], g[prefix + "norm1.bias"], dyT_next = ops.layernorm_bwd_fused(sv["x2"], f("norm1.weight"), dxn, B, H, W, add=dx1, windowed=True,
-                                                                                                     shift=shift, cast=dict(scale=next_scale, windowed=False))
-        side.join()
-        return dx.reshape(B, L, C), g, dyT_next
-    dx, g[prefix + "norm1.weight"], g[prefix + "norm1.bias"] = ops.layernorm_bwd_fused(sv["x2"], f("norm1.weight"), dxn, B, H, W, add=dx1, windowed=True, shift=shift)
+        g[prefix + "modulator.weight"] = side.run(lambda: ops.rows_sum(dxn.reshape(B * L // 64, 64 * C)).reshape(64, C))
+    # LN1 backward reads dxn in the branch's order (window_reverse + roll back folded in), adds the residual path's gradient and, when asked,
+    # writes T(dx * next_scale) for the block that ran before this one
+    cast = dict(scale=next_scale, windowed=False) if next_scale is not _NO_CAST and _FUSE_FORK and dxn.dtype == T else None
+    dx, g[prefix + "norm1.weight"], g[prefix + "norm1.bias"], *dyT_next = ops.layernorm_bwd_fused(sv["x2"], f("norm1.weight"), dxn, B, H, W, add=dx1, cast=cast, **rows)
     side.join()
-    if next_scale is not _NO_CAST:
-        return dx.reshape(B, L, C), g, None
-    return dx.reshape(B, L, C), g
-
-
-def _mlp_block_backward(sv: Saved, dyf: Tensor, dyT: Tensor, next_scale, side: "_Side", g: Grads):
-    """lewin_block_backward for a block whose feed-forward half is the reference's Mlp: fc2 -> GELU -> fc1 (model.py:636-642), then the
-    8x8-window attention half exactly as for a LeFF block.  Composed from the entry points the LeFF tape uses: uf_linear_wgrad, the
-    input-gradient GEMM with the GELU' epilogue (uf_linear_mul_dgelu), the fused LayerNorm backward."""
-    p, prefix, heads, shift, T = sv["p"], sv["prefix"], sv["heads"], sv["shift"], sv["T"]
-    B, L, C = sv["shape"]
-    H, W = sv["hw"]
-    M = B * L
-    f = lambda k: p[prefix + k]                                             # noqa: E731
-    pk: BlockPack = sv["pk"]
-    h = ops.gelu(sv["a1"])                                                  # T(GELU(a1)), recomputed: what fc2 read in the forward
-    g[prefix + "mlp.fc2.weight"], g[prefix + "mlp.fc2.bias"] = side.run(lambda: ops.linear_wgrad(dyT, h))
-    da1 = ops.linear_mul_dgelu(dyT, pk.w2_t, _zeros(4 * C, dyT.device), sv["a1"])       # dY W2, times GELU'(a1)
-    g[prefix + "mlp.fc1.weight"], g[prefix + "mlp.fc1.bias"] = side.run(lambda: ops.linear_wgrad(da1, sv["z"]))
-    dz = _input_grad(da1, pk.w1_t)
-    if _FUSE_FORK and dz.dtype == T:
-        dx1, g[prefix + "norm2.weight"], g[prefix + "norm2.bias"], dyw = ops.layernorm_bwd_fused(sv["x1"], f("norm2.weight"), dz, B, H, W, add=dyf,
-                                                                                                 cast=dict(scale=sv["s1"], windowed=True, shift=shift))
-    else:
-        dx1, g[prefix + "norm2.weight"], g[prefix + "norm2.bias"] = ops.layernorm_bwd_fused(sv["x1"], f("norm2.weight"), dz, B, H, W)
-        dx1, dyw = ops.grad_fork(dx1, dyf, sv["s1"], B, H, W, T, windowed=True, shift=shift, want_sum=True)
-    g[prefix + "attn.proj.weight"], g[prefix + "attn.proj.bias"] = side.run(lambda: ops.linear_wgrad(dyw, sv["o"]))
-    do = _input_grad(dyw, pk.wp_t)
-    dqkv, dbias = ops.window_attention_bwd_qkv(sv["q"], sv["k"], sv["vt"], pk.bias, do, H, W, shift)
-    g[prefix + "attn.relative_position_bias_table"] = side.run(lambda: ops.rpb_table_grad(dbias))
-    dWqkv, dbqkv = side.run(lambda: ops.linear_wgrad(dqkv, sv["xn"]))
-    g[prefix + "attn.qkv.to_q.weight"], g[prefix + "attn.qkv.to_kv.weight"] = dWqkv[:C], dWqkv[C:]
-    g[prefix + "attn.qkv.to_q.bias"], g[prefix + "attn.qkv.to_kv.bias"] = dbqkv[:C], dbqkv[C:]
-    dxn = _input_grad(dqkv, pk.wqkv_t)
-    if sv["mod"]:
-        g[prefix + "modulator.weight"] = side.run(lambda: ops.rows_sum(dxn.reshape(M // 64, 64 * C)).reshape(64, C))
-    dyT_next = None
-    if next_scale is not _NO_CAST and _FUSE_FORK and dxn.dtype == T:
-        dx, g[prefix + "norm1.weight"], g[prefix + "norm1.bias"], dyT_next = ops.layernorm_bwd_fused(sv["x2"], f("norm1.weight"), dxn, B, H, W, add=dx1, windowed=True,
-                                                                                                     shift=shift, cast=dict(scale=next_scale, windowed=False))
-    else:
-        dx, g[prefix + "norm1.weight"], g[prefix + "norm1.bias"] = ops.layernorm_bwd_fused(sv["x2"], f("norm1.weight"), dxn, B, H, W, add=dx1, windowed=True, shift=shift)
-    side.join()
-    if next_scale is not _NO_CAST:
-        return dx.reshape(B, L, C), g, dyT_next
-    return dx.reshape(B, L, C), g
+    if next_scale is _NO_CAST:
+        return dx.reshape(B, L, C), g
+    return dx.reshape(B, L, C), g, dyT_next[0] if dyT_next else None
 
 
 def _named_block_grads(prefix: str, gv: Dict[str, Tensor], C: int) -> Grads:
@@ -666,37 +644,25 @@ class UformerTape:
                 bi = first[s] + i
                 prefix = f"{STAGES[s]}.blocks.{i}."
                 dr = self.drop[2 * bi:2 * bi + 2] if self.drop is not None else None
-                # the fused kernels (and the block-level C backward built on them) cover head_dim 32; a head_dim-16 block (Uformer_T,
-                # utils/model_utils.py:66-67) or head_dim-64 block (embed_dim 64) takes the op-by-op forward that keeps its intermediates and the
-                # op-level backward
-                # (a 4x4-window block -- the bottleneck of a model built for 64x64 patches -- keeps its intermediates in both forms)
-                # (an Mlp block -- token_mlp 'ffn' -- has no block-level C backward and no native pack: it is packed through BlockPack and, in the
-                #  recompute form, reruns its op-by-op forward like a head_dim-64 block)
-                is_mlp = block_is_mlp(sd, prefix)
-                fusable = self.recompute and C == 32 * cfg.num_heads[s] and wins[s] == 8 and not is_mlp
-                # uf_pack_block_train (5 launches) covers C % 32 == 0; its pack also serves the op-by-op form as tensor views
-                native = C % 32 == 0 and C % cfg.num_heads[s] == 0 and _NATIVE_PACK and wins[s] == 8 and not is_mlp
-                if wins[s] == 4 and C % 32 == 0 and _NATIVE_PACK and not is_mlp:
-                    pk = self.packs[prefix] = native_block4_pack(sd, prefix, cfg.num_heads[s], T)
+                heads, L = cfg.num_heads[s], res[s][0] * res[s][1]
+                pack, run = block_form(self.recompute, T, C, heads, wins[s], block_is_mlp(sd, prefix))
+                if pack == "native4":
+                    pk = native_block4_pack(sd, prefix, heads, T)
+                elif pack == "native":
+                    pk = NativeBlockPack(sd, prefix, heads, shifts[s][i], T)
                 else:
-                    pk = self.packs[prefix] = (NativeBlockPack(sd, prefix, cfg.num_heads[s], shifts[s][i], T) if native else
-                                               BlockPack(sd, prefix, cfg.num_heads[s], shifts[s][i], T, fused=fusable or fused_attn_covers(T, C, cfg.num_heads[s])))
-                # a head_dim-64 block in the recompute form: the op-by-op forward, of which only the block's input is kept; its backward
-                # reruns the same unfused pieces (need_y=False: up to the stencil) and differentiates them -- the same kernels on the same
-                # operands as the kept form, so the same bits
-                unfused_rc = self.recompute and wins[s] == 8 and (C == 64 * cfg.num_heads[s] or (is_mlp and C == 32 * cfg.num_heads[s]))
-                if unfused_rc:
-                    y, _ = lewin_block_forward(t.reshape(B, res[s][0] * res[s][1], C), sd, prefix, cfg.num_heads[s], shifts[s][i], T, dr, pk, hw=res[s])
-                    self.saved_blocks[s].append(dict(x=t, drop=dr, pk=pk, unfused=(prefix, cfg.num_heads[s], shifts[s][i], res[s])))
-                    t = y.reshape(-1, C)
-                elif fusable:                                                   # fused kernels; the block's input is all that is kept
+                    pk = BlockPack(sd, prefix, heads, shifts[s][i], T, fused=pack[1])
+                self.packs[prefix] = pk
+                if run == "recompute_fused":                                    # fused kernels; the block's input is all that is kept
                     y = ops.lewin_block_train_fwd(pk.fused, t, B, res[s][0], res[s][1], T, None if dr is None else dr[0], None if dr is None else dr[1])
-                    self.saved_blocks[s].append(dict(x=t, drop=dr, pk=pk))
-                    t = y
+                    sv = dict(x=t, drop=dr, pk=pk)
                 else:
-                    y, sv = lewin_block_forward(t.reshape(B, res[s][0] * res[s][1], C), sd, prefix, cfg.num_heads[s], shifts[s][i], T, dr, pk, hw=res[s])
-                    self.saved_blocks[s].append(sv)
-                    t = y.reshape(-1, C)
+                    y, sv = lewin_block_forward(t.reshape(B, L, C), sd, prefix, heads, shifts[s][i], T, dr, pk, hw=res[s])
+                    if run == "recompute_unfused":                              # of the op-by-op forward, only the block's input is kept
+                        sv = dict(x=t, drop=dr, pk=pk)
+                sv["form"] = run
+                self.saved_blocks[s].append(sv)
+                t = y.reshape(-1, C)
             return t
 
         # the samplers / stem / head run their inference kernels; their inputs are kept
@@ -752,18 +718,18 @@ class UformerTape:
             dyT = None                                                            # T(d * s2 of the block about to run): from the previous block's LN1 backward
             while blocks:
                 sv = blocks.pop()                                                 # frees the block's saved input as the sweep passes it
-                if "unfused" in sv:                                               # head_dim 64: only the block input was kept; rerun the op-by-op forward, then the op-level backward
-                    prefix_, heads_, shift_, hw_ = sv["unfused"]
-                    _, sv2 = lewin_block_forward(sv["x"].reshape(B, hw_[0] * hw_[1], C), sd, prefix_, heads_, shift_, T, sv["drop"], sv["pk"], need_y=False, hw=hw_)
+                form, pk = sv["form"], sv["pk"]                                   # block_form's ``run``
+                if form == "recompute_unfused":                                   # rerun the op-by-op forward, then the op-level backward
+                    _, sv2 = lewin_block_forward(sv["x"].reshape(d.shape), sd, pk.prefix, pk.heads, pk.shift, T, sv["drop"], pk, need_y=False, hw=res[s])
                     d, gb = lewin_block_backward(sv2, d, None)
                     dyT = None
                     del sv2
-                elif "x2" not in sv:                                              # only the block input was kept: recomputation + backward in one C call
-                    pk, dr = sv["pk"], sv["drop"]
+                elif form == "recompute_fused":                                   # recomputation + backward in one C call
+                    dr = sv["drop"]
                     dxb, gv = ops.lewin_block_bwd(pk.train_params, sv["x"], d.reshape(-1, C), None if dr is None else dr[0], None if dr is None else dr[1],
                                                   B, res[s][0], res[s][1], pk.heads, T, ws=self._block_ws(s))
-                    d, gb = dxb.reshape(B, res[s][0] * res[s][1], C), _named_block_grads(pk.prefix, gv, C)
-                elif blocks and "x2" in blocks[-1]:                               # the block that ran before this one reads T(d * its s2): made here
+                    d, gb = dxb.reshape(d.shape), _named_block_grads(pk.prefix, gv, C)
+                elif blocks and blocks[-1]["form"] == "kept":                     # the block that ran before this one reads T(d * its s2): made here
                     d, gb, dyT = lewin_block_backward(sv, d, dyT, next_scale=blocks[-1]["s2"])
                 else:
                     d, gb = lewin_block_backward(sv, d, dyT)
