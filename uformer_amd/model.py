@@ -502,8 +502,7 @@ class LeWinTransformerBlock(nn.Module):
                 nbytes = lib.uf_block_workspace_bytes(B * L, Cc, dt)
                 ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
                 bp = self._pack(compute_dtype)
-                _lib.check(lib.uf_lewin_block4_fwd(bp, y.data_ptr(), Cc, B, H, W, Cc, None, None, dt, ws.data_ptr(), nbytes,
-                                                   torch.cuda.current_stream().cuda_stream), "uf_lewin_block4_fwd")
+                ops._launch("uf_lewin_block4_fwd", x.device, bp, y, Cc, B, H, W, Cc, None, None, dt, ws, nbytes)
             return y.to(x.dtype)
         um = self.user_attn_mask(mask, H, W) if mask is not None else None
         with torch.cuda.device(x.device):
@@ -512,11 +511,8 @@ class LeWinTransformerBlock(nn.Module):
             ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
             bp = self._pack(compute_dtype)
             if self.cross_modulator is not None:    # model.py:945-949, on the un-normalised stream, before the attention half
-                _lib.check(lib.uf_cross_attn_fwd(self._pack_cross(compute_dtype), y.data_ptr(), Cc, B * L, Cc, dt,
-                                                 torch.cuda.current_stream().cuda_stream), "uf_cross_attn_fwd")
-            _lib.check(lib.uf_lewin_block_fwd(bp, y.data_ptr(), Cc, B, H, W, Cc, None if um is None else um.data_ptr(),
-                                              0 if um is None else um.shape[0], dt, ws.data_ptr(), nbytes,
-                                              torch.cuda.current_stream().cuda_stream), "uf_lewin_block_fwd")
+                ops._launch("uf_cross_attn_fwd", x.device, self._pack_cross(compute_dtype), y, Cc, B * L, Cc, dt)
+            ops._launch("uf_lewin_block_fwd", x.device, bp, y, Cc, B, H, W, Cc, um, 0 if um is None else um.shape[0], dt, ws, nbytes)
         return y.to(x.dtype)
 
 
@@ -773,16 +769,14 @@ class Uformer(nn.Module):
                     raise UformerHipError("uf_uformer_win4_workspace_bytes: " + _lib.last_error())
                 ws = self._workspace(need, x.device)
                 out = torch.empty((B, self.in_chans, H, W), dtype=torch.float32, device=x.device)
-                _lib.check(lib.uf_uformer_win4_fwd(pk.desc, pk.bneck, xin.data_ptr(), out.data_ptr(), B, H, W, dt, ws.data_ptr(),
-                                                   ws.numel(), torch.cuda.current_stream().cuda_stream), "uf_uformer_win4_fwd")
+                ops._launch("uf_uformer_win4_fwd", x.device, pk.desc, pk.bneck, xin, out, B, H, W, dt, ws, ws.numel())
                 return out.to(x.dtype)
             need = lib.uf_uformer_workspace_bytes(pk.desc, B, H, W, dt)
             if need == 0:
                 raise UformerHipError("uf_uformer_workspace_bytes: " + _lib.last_error())
             ws = self._workspace(need, x.device)
             out = torch.empty((B, self.in_chans, H, W), dtype=torch.float32, device=x.device)
-            _lib.check(lib.uf_uformer_fwd(pk.desc, xin.data_ptr(), out.data_ptr(), B, H, W, dt, ws.data_ptr(),
-                                          ws.numel(), torch.cuda.current_stream().cuda_stream), "uf_uformer_fwd")
+            ops._launch("uf_uformer_fwd", x.device, pk.desc, xin, out, B, H, W, dt, ws, ws.numel())
         return out.to(x.dtype)
 
     def drop_path_rates(self):
@@ -968,8 +962,7 @@ class UNet(nn.Module):
                 raise UformerHipError("uf_unet_workspace_bytes: " + _lib.last_error())
             ws = self._workspace(need, x.device)
             out = torch.empty((B, 3, H, W), dtype=torch.float32, device=x.device)
-            _lib.check(lib.uf_unet_fwd(pk.desc, xin.data_ptr(), out.data_ptr(), B, H, W, dt, ws.data_ptr(), ws.numel(),
-                                       torch.cuda.current_stream().cuda_stream), "uf_unet_fwd")
+            ops._launch("uf_unet_fwd", x.device, pk.desc, xin, out, B, H, W, dt, ws, ws.numel())
         return out.to(x.dtype)
 
     def flops(self, H, W):

@@ -1,12 +1,13 @@
 """Thin torch-tensor wrappers over the C ABI (``include/uformer_hip.h``).
 
-PyTorch is plumbing here: it owns device memory and the HIP stream; every wrapper extracts
-raw pointers and calls ``libuformer_hip.so``.  No op has a CPU or eager fallback -- CPU tensors
+PyTorch is plumbing here: it owns device memory and the HIP stream; every wrapper hands its tensors to ``_launch``, which
+extracts the raw pointers and calls ``libuformer_hip.so``.  No op has a CPU or eager fallback -- CPU tensors
 raise.  Names follow the reference functions they replace (model.py:704-726 etc.).
 """
 from __future__ import annotations
 
-from typing import Optional
+import ctypes
+from typing import Optional, Tuple
 
 import torch
 
@@ -53,15 +54,23 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def _launch(name: str, dev, *args) -> None:
+    """Call entry point ``name`` on ``dev``'s current stream: a Tensor argument goes as its address (None as NULL), anything else as it
+    is, the stream last.  ``args`` holds every tensor until the call has returned, so a wrapper may build a converted operand
+    (``_c``, ``_f32``, ``_pack_frag``) right in the argument list; it never takes an address itself."""
+    with torch.cuda.device(dev):
+        # hasattr, not isinstance: half the cost per scalar argument, and a step makes several hundred launches
+        rc = getattr(_lib.load(), name)(*[a.data_ptr() if hasattr(a, "data_ptr") else a for a in args], _stream())
+    _lib.check(rc, name)
+
+
 def _pack_frag(w: Tensor) -> Tensor:
     """Row-major nn.Linear weight -> the fragment-major layout the fused kernels stream (uf_pack_weight_fm)."""
     _dev(w)
     w = _c(w)
     N, K = w.shape
-    lib = _lib.load()
-    out = torch.empty(lib.uf_weight_fm_elems(N, K), dtype=w.dtype, device=w.device)
-    with torch.cuda.device(w.device):
-        _lib.check(lib.uf_pack_weight_fm(_ptr(w), _ptr(out), N, K, uf_dtype(w.dtype), _stream()), "uf_pack_weight_fm")
+    out = torch.empty(_lib.load().uf_weight_fm_elems(N, K), dtype=w.dtype, device=w.device)
+    _launch("uf_pack_weight_fm", w.device, w, out, N, K, uf_dtype(w.dtype))
     return out
 
 
@@ -69,6 +78,21 @@ def _c(t: Tensor, dtype: Optional[torch.dtype] = None) -> Tensor:
     if dtype is not None and t.dtype != dtype:
         t = t.to(dtype)
     return t if t.is_contiguous() else t.contiguous()
+
+
+def _f32(t: Optional[Tensor]) -> Optional[Tensor]:
+    return None if t is None else _c(t, torch.float32)
+
+
+def _ws(nbytes: int, device) -> Tensor:
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+
+
+def _workspace(query: str, device, *dims) -> Tuple[Tensor, int]:
+    """(workspace tensor, its size in bytes as the entry point wants it) from the size query ``query(*dims)``; ``*_workspace(...)``
+    fills the two C arguments."""
+    nbytes = getattr(_lib.load(), query)(*dims)
+    return _ws(nbytes, device), nbytes
 
 
 # ---------------------------------------------------------------------------------------
@@ -87,9 +111,7 @@ def window_partition(x: Tensor, win_size: int = 8, shift: int = 0) -> Tensor:
     if x.element_size() not in (2, 4):
         raise UformerHipError("window ops support 2- and 4-byte elements")
     out = torch.empty((B * (H // 8) * (W // 8), 8, 8, Cc), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().uf_window_partition(_ptr(x), _ptr(out), B, H, W, Cc, shift, x.element_size(), _stream()),
-                   "uf_window_partition")
+    _launch("uf_window_partition", x.device, x, out, B, H, W, Cc, shift, x.element_size())
     return out
 
 
@@ -105,9 +127,7 @@ def window_reverse(windows: Tensor, win_size: int, H: int, W: int, shift: int = 
     nW = (H // 8) * (W // 8)
     B = windows.shape[0] // nW
     out = torch.empty((B, H, W, Cc), dtype=windows.dtype, device=windows.device)
-    with torch.cuda.device(windows.device):
-        _lib.check(_lib.load().uf_window_reverse(_ptr(windows), _ptr(out), B, H, W, Cc, shift, windows.element_size(),
-                                                 _stream()), "uf_window_reverse")
+    _launch("uf_window_reverse", windows.device, windows, out, B, H, W, Cc, shift, windows.element_size())
     return out
 
 
@@ -129,8 +149,7 @@ def _window4_copy(x: Tensor, reverse: bool, H: int = 0, W: int = 0) -> Tensor:
         B, H, W, _ = x.shape
         out = torch.empty((B * (H // 4) * (W // 4), 4, 4, Cc), dtype=x.dtype, device=x.device)
         fn = "uf_window4_partition"
-    with torch.cuda.device(x.device):
-        _lib.check(getattr(_lib.load(), fn)(_ptr(x), _ptr(out), B, H, W, Cc, x.element_size(), _stream()), fn)
+    _launch(fn, x.device, x, out, B, H, W, Cc, x.element_size())
     return out
 
 
@@ -144,9 +163,7 @@ def window4_attention(qkv: Tensor, rpb4: Tensor, B: int, H: int, W: int, heads: 
     if M != B * H * W or C3 != 3 * C:
         raise UformerHipError(f"window4_attention: qkv {tuple(qkv.shape)} does not match B*H*W = {B * H * W}")
     out = torch.empty(M, C, dtype=qkv.dtype, device=qkv.device)
-    with torch.cuda.device(qkv.device):
-        _lib.check(_lib.load().uf_window4_attention_fwd(_ptr(qkv), C3, _ptr(_c(rpb4, torch.float32)), _ptr(out), C, B, H, W, C, heads,
-                                                        uf_dtype(qkv.dtype), _stream()), "uf_window4_attention_fwd")
+    _launch("uf_window4_attention_fwd", qkv.device, qkv, C3, _f32(rpb4), out, C, B, H, W, C, heads, uf_dtype(qkv.dtype))
     return out
 
 
@@ -161,9 +178,7 @@ def window4_attention_bwd(qkv: Tensor, rpb4: Tensor, do: Tensor, B: int, H: int,
         raise UformerHipError(f"window4_attention_bwd: qkv {tuple(qkv.shape)} / do {tuple(do.shape)} do not match B*H*W = {B * H * W}")
     dqkv = torch.empty_like(qkv)
     dscore = torch.empty(B * (H // 4) * (W // 4), heads, 16, 16, dtype=torch.float32, device=qkv.device)
-    with torch.cuda.device(qkv.device):
-        _lib.check(_lib.load().uf_window4_attention_bwd(_ptr(qkv), C3, _ptr(_c(rpb4, torch.float32)), _ptr(do), C, _ptr(dqkv), C3, _ptr(dscore),
-                                                        B, H, W, C, heads, uf_dtype(qkv.dtype), _stream()), "uf_window4_attention_bwd")
+    _launch("uf_window4_attention_bwd", qkv.device, qkv, C3, _f32(rpb4), do, C, dqkv, C3, dscore, B, H, W, C, heads, uf_dtype(qkv.dtype))
     return dqkv, dscore
 
 
@@ -173,16 +188,14 @@ def rpb4_table_grad(dscore: Tensor) -> Tensor:
     dscore = _c(dscore, torch.float32)
     nW, heads = dscore.shape[0], dscore.shape[1]
     out = torch.empty(49, heads, dtype=torch.float32, device=dscore.device)
-    with torch.cuda.device(dscore.device):
-        _lib.check(_lib.load().uf_rpb4_table_grad(_ptr(dscore), _ptr(out), nW, heads, _stream()), "uf_rpb4_table_grad")
+    _launch("uf_rpb4_table_grad", dscore.device, dscore, out, nW, heads)
     return out
 
 
 def shift_mask(H: int, W: int, shift: int, device) -> Tensor:
     """SW-MSA mask (nW,64,64) in {0,-100}.  model.py:924-942."""
     out = torch.empty(((H // 8) * (W // 8), 64, 64), dtype=torch.float32, device=device)
-    with torch.cuda.device(out.device):
-        _lib.check(_lib.load().uf_shift_mask(_ptr(out), H, W, shift, _stream()), "uf_shift_mask")
+    _launch("uf_shift_mask", out.device, out, H, W, shift)
     return out
 
 
@@ -197,11 +210,7 @@ def layernorm(x: Tensor, gamma: Tensor, beta: Tensor, *, B: int, H: int, W: int,
     x = _c(x, torch.float32)
     Cc = x.shape[-1]
     out = torch.empty((B * H * W, Cc), dtype=torch_dtype(dt), device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().uf_layernorm_fwd(_ptr(x), Cc, _ptr(_c(gamma, torch.float32)), _ptr(_c(beta, torch.float32)),
-                                                _ptr(None if modulator is None else _c(modulator, torch.float32)),
-                                                _ptr(out), B, H, W, Cc, int(windowed), shift, dt, _stream()),
-                   "uf_layernorm_fwd")
+    _launch("uf_layernorm_fwd", x.device, x, Cc, _f32(gamma), _f32(beta), _f32(modulator), out, B, H, W, Cc, int(windowed), shift, dt)
     return out
 
 
@@ -213,9 +222,7 @@ def linear(a: Tensor, w: Tensor, bias: Tensor, act: int = 0) -> Tensor:
     M, K = a.shape
     N = w.shape[0]
     out = torch.empty((M, N), dtype=a.dtype, device=a.device)
-    with torch.cuda.device(a.device):
-        _lib.check(_lib.load().uf_linear_fwd(_ptr(a), _ptr(w), _ptr(_c(bias, torch.float32)), _ptr(out), M, N, K, act, dt,
-                                             _stream()), "uf_linear_fwd")
+    _launch("uf_linear_fwd", a.device, a, w, _f32(bias), out, M, N, K, act, dt)
     return out
 
 
@@ -230,11 +237,9 @@ def linear_residual(a: Tensor, w: Tensor, bias: Tensor, resid: Tensor, scale: Op
     N = w.shape[0]
     if M != B * H * W or resid.numel() != M * N:
         raise UformerHipError(f"linear_residual: a {tuple(a.shape)} / resid {tuple(resid.shape)} do not match B*H*W = {B * H * W}, N = {N}")
-    sc = None if scale is None else _c(scale, torch.float32)
+    sc = _f32(scale)
     out = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    with torch.cuda.device(a.device):
-        _lib.check(_lib.load().uf_linear_residual_fwd(_ptr(a), _ptr(w), _ptr(_c(bias, torch.float32)), _ptr(resid), _ptr(out), _ptr(sc) if sc is not None else None,
-                                                      B, H, W, N, K, int(windowed), shift, dt, _stream()), "uf_linear_residual_fwd")
+    _launch("uf_linear_residual_fwd", a.device, a, w, _f32(bias), resid, out, sc, B, H, W, N, K, int(windowed), shift, dt)
     return out
 
 
@@ -248,9 +253,7 @@ def qkv(a: Tensor, wqkv: Tensor, bqkv: Tensor, heads: int):
     q = torch.empty((M // 64, heads, 64, hd), dtype=a.dtype, device=a.device)
     k = torch.empty_like(q)
     vt = torch.empty((M // 64, heads, hd, 64), dtype=a.dtype, device=a.device)
-    with torch.cuda.device(a.device):
-        _lib.check(_lib.load().uf_qkv_fwd(_ptr(a), _ptr(wqkv), _ptr(_c(bqkv, torch.float32)), _ptr(q), _ptr(k), _ptr(vt), M,
-                                          Cc, heads, dt, _stream()), "uf_qkv_fwd")
+    _launch("uf_qkv_fwd", a.device, a, wqkv, _f32(bqkv), q, k, vt, M, Cc, heads, dt)
     return q, k, vt
 
 
@@ -265,11 +268,8 @@ def ln_qkv(x: Tensor, gamma: Tensor, beta: Tensor, wqkv: Tensor, bqkv: Tensor, h
     q = torch.empty((M // 64, heads, 64, hd), dtype=wqkv.dtype, device=x.device)
     k = torch.empty_like(q)
     vt = torch.empty((M // 64, heads, hd, 64), dtype=wqkv.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().uf_ln_qkv_fwd(_ptr(x), Cc, _ptr(_c(gamma, torch.float32)), _ptr(_c(beta, torch.float32)),
-                                             _ptr(None if modulator is None else _c(modulator, torch.float32)), _ptr(_pack_frag(wqkv)),
-                                             _ptr(_c(bqkv, torch.float32)), _ptr(q), _ptr(k), _ptr(vt), B, H, W, Cc, heads, shift,
-                                             dt, _stream()), "uf_ln_qkv_fwd")
+    _launch("uf_ln_qkv_fwd", x.device, x, Cc, _f32(gamma), _f32(beta), _f32(modulator), _pack_frag(wqkv), _f32(bqkv), q, k, vt,
+            B, H, W, Cc, heads, shift, dt)
     return q, k, vt
 
 
@@ -291,11 +291,8 @@ def ln_conv_qkv(x: Tensor, gamma: Tensor, beta: Tensor, dw9: Tensor, bdw: Tensor
     q = torch.empty((M // 64, heads, 64, hd), dtype=wpw.dtype, device=x.device)
     k = torch.empty_like(q)
     vt = torch.empty((M // 64, heads, hd, 64), dtype=wpw.dtype, device=x.device)
-    keep = (_c(gamma, torch.float32), _c(beta, torch.float32), None if modulator is None else _c(modulator, torch.float32), _c(dw9, torch.float32),
-            _c(bdw, torch.float32), _pack_frag(wpw), _c(bpw, torch.float32))
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().uf_ln_convqkv_fwd(_ptr(x), ld, *[_ptr(t) for t in keep], _ptr(q), _ptr(k), _ptr(vt), B, H, W, Cc, heads, shift, dt,
-                                                 _stream()), "uf_ln_convqkv_fwd")
+    _launch("uf_ln_convqkv_fwd", x.device, x, ld, _f32(gamma), _f32(beta), _f32(modulator), _f32(dw9), _f32(bdw), _pack_frag(wpw), _f32(bpw),
+            q, k, vt, B, H, W, Cc, heads, shift, dt)
     return q, k, vt
 
 
@@ -307,10 +304,7 @@ def ln_linear_gelu(x: Tensor, gamma: Tensor, beta: Tensor, w1: Tensor, b1: Tenso
     M, Cc = x.shape
     N = w1.shape[0]
     out = torch.empty((M, N), dtype=w1.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().uf_ln_linear_gelu_fwd(_ptr(x), Cc, _ptr(_c(gamma, torch.float32)), _ptr(_c(beta, torch.float32)),
-                                                     _ptr(_pack_frag(w1)), _ptr(_c(b1, torch.float32)), _ptr(out), M, N, Cc, dt, _stream()),
-                   "uf_ln_linear_gelu_fwd")
+    _launch("uf_ln_linear_gelu_fwd", x.device, x, Cc, _f32(gamma), _f32(beta), _pack_frag(w1), _f32(b1), out, M, N, Cc, dt)
     return out
 
 
@@ -327,11 +321,8 @@ def ffn(x: Tensor, gamma: Tensor, beta: Tensor, w1: Tensor, b1: Tensor, w2: Tens
     Cc = ld if C is None else int(C)
     if tuple(w1.shape) != (4 * Cc, Cc) or tuple(w2.shape) != (Cc, 4 * Cc):
         raise UformerHipError(f"ffn: w1 {tuple(w1.shape)} / w2 {tuple(w2.shape)} do not match C = {Cc}")
-    keep = (_c(gamma, torch.float32), _c(beta, torch.float32), _pack_frag(w1), _c(b1, torch.float32), _pack_frag(_c(w2, w1.dtype)), _c(b2, torch.float32),
-            None if scale is None else _c(scale, torch.float32))
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().uf_ffn_fwd(_ptr(x), ld, _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), _ptr(keep[3]), _ptr(keep[4]), _ptr(keep[5]),
-                                          _ptr(keep[6]), B, M, Cc, dt, _stream()), "uf_ffn_fwd")
+    _launch("uf_ffn_fwd", x.device, x, ld, _f32(gamma), _f32(beta), _pack_frag(w1), _f32(b1), _pack_frag(_c(w2, w1.dtype)), _f32(b2), _f32(scale),
+            B, M, Cc, dt)
     return x
 
 
@@ -349,13 +340,13 @@ def cross_attn(x: Tensor, wq: Tensor, bq: Tensor, k: Tensor, vt: Tensor, wp: Ten
     heads, nk, hd = k.shape
     if tuple(wq.shape) != (Cc, Cc) or tuple(wp.shape) != (Cc, Cc) or nk != 64 or heads * hd != Cc or tuple(vt.shape) != (heads, hd, 64):
         raise UformerHipError(f"cross_attn: wq {tuple(wq.shape)} / wp {tuple(wp.shape)} / k {tuple(k.shape)} / vt {tuple(vt.shape)} do not match C = {Cc}")
-    keep = (_pack_frag(wq), _c(bq, torch.float32), _c(k, wq.dtype), _c(vt, wq.dtype), _pack_frag(_c(wp, wq.dtype)), _c(bp, torch.float32))
+    # the struct holds addresses, not tensors: ``fields`` owns the operands until the call has returned
+    fields = (_pack_frag(wq), _c(bq, torch.float32), _c(k, wq.dtype), _c(vt, wq.dtype), _pack_frag(_c(wp, wq.dtype)), _c(bp, torch.float32))
     cp = _lib.CrossParams()
-    for name, tns in zip(("wq_fm", "bq", "k", "vt", "wp_fm", "bp"), keep):
+    for name, tns in zip(("wq_fm", "bq", "k", "vt", "wp_fm", "bp"), fields):
         setattr(cp, name, _ptr(tns))
     cp.heads = int(heads)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().uf_cross_attn_fwd(cp, _ptr(x), ld, M, Cc, dt, _stream()), "uf_cross_attn_fwd")
+    _launch("uf_cross_attn_fwd", x.device, cp, x, ld, M, Cc, dt)
     return x
 
 
@@ -366,12 +357,9 @@ def window_attention_core(q: Tensor, k: Tensor, vt: Tensor, bias_dense: Tensor, 
     dt = uf_dtype(q.dtype)
     nwin, heads, _, hd = q.shape
     out = torch.empty((nwin * 64, heads * hd), dtype=q.dtype, device=q.device)
-    if mask is not None:
-        mask = _c(mask, torch.float32)
-    with torch.cuda.device(q.device):
-        _lib.check(_lib.load().uf_window_attention_fwd(_ptr(_c(q)), _ptr(_c(k)), _ptr(_c(vt)), _ptr(_c(bias_dense, torch.float32)),
-                                                       _ptr(mask), 0 if mask is None else mask.shape[0], _ptr(out), nwin,
-                                                       heads, hd, H, W, shift, dt, _stream()), "uf_window_attention_fwd")
+    mask = _f32(mask)
+    _launch("uf_window_attention_fwd", q.device, _c(q), _c(k), _c(vt), _f32(bias_dense), mask, 0 if mask is None else mask.shape[0], out,
+            nwin, heads, hd, H, W, shift, dt)
     return out
 
 
@@ -382,9 +370,7 @@ def dwconv3x3_gelu(x: Tensor, w9: Tensor, bias: Tensor) -> Tensor:
     x = _c(x)
     B, H, W, Cc = x.shape
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().uf_dwconv3x3_gelu_fwd(_ptr(x), _ptr(_c(w9, torch.float32)), _ptr(_c(bias, torch.float32)),
-                                                     _ptr(out), B, H, W, Cc, dt, _stream()), "uf_dwconv3x3_gelu_fwd")
+    _launch("uf_dwconv3x3_gelu_fwd", x.device, x, _f32(w9), _f32(bias), out, B, H, W, Cc, dt)
     return out
 
 
@@ -396,10 +382,7 @@ def dwconv3x3(x: Tensor, w9: Tensor, bias: Optional[Tensor] = None, gelu: bool =
     x = _c(x)
     B, H, W, Cc = x.shape
     out = torch.empty_like(x)
-    b = _c(bias, torch.float32) if bias is not None else None
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().uf_dwconv3x3_fwd(_ptr(x), _ptr(_c(w9, torch.float32)), _ptr(b) if b is not None else None, _ptr(out),
-                                                B, H, W, Cc, 1 if gelu else 0, dt, _stream()), "uf_dwconv3x3_fwd")
+    _launch("uf_dwconv3x3_fwd", x.device, x, _f32(w9), _f32(bias), out, B, H, W, Cc, 1 if gelu else 0, dt)
     return out
 
 
@@ -411,10 +394,8 @@ def dwconv3x3_pre_gelu(x: Tensor, w9: Tensor, bias: Tensor, gelu_in: bool = Fals
     x = _c(x)
     B, H, W, Cc = x.shape
     pre, act = torch.empty_like(x), torch.empty_like(x)
-    lib = _lib.load()
-    fn, name = (lib.uf_dwconv3x3_gelu_in_pre_gelu_fwd, "uf_dwconv3x3_gelu_in_pre_gelu_fwd") if gelu_in else (lib.uf_dwconv3x3_pre_gelu_fwd, "uf_dwconv3x3_pre_gelu_fwd")
-    with torch.cuda.device(x.device):
-        _lib.check(fn(_ptr(x), _ptr(_c(w9, torch.float32)), _ptr(_c(bias, torch.float32)), _ptr(pre), _ptr(act), B, H, W, Cc, uf_dtype(x.dtype), _stream()), name)
+    _launch("uf_dwconv3x3_gelu_in_pre_gelu_fwd" if gelu_in else "uf_dwconv3x3_pre_gelu_fwd", x.device, x, _f32(w9), _f32(bias), pre, act,
+            B, H, W, Cc, uf_dtype(x.dtype))
     return pre, act
 
 
@@ -424,9 +405,7 @@ def dwconv3x3_mul_dgelu(dy: Tensor, w9_flipped: Tensor, pre: Tensor) -> Tensor:
     dy, pre = _c(dy), _c(pre, dy.dtype)
     B, H, W, Cc = dy.shape
     out = torch.empty_like(dy)
-    with torch.cuda.device(dy.device):
-        _lib.check(_lib.load().uf_dwconv3x3_mul_dgelu(_ptr(dy), _ptr(_c(w9_flipped, torch.float32)), _ptr(pre), _ptr(out), B, H, W, Cc,
-                                                      uf_dtype(dy.dtype), _stream()), "uf_dwconv3x3_mul_dgelu")
+    _launch("uf_dwconv3x3_mul_dgelu", dy.device, dy, _f32(w9_flipped), pre, out, B, H, W, Cc, uf_dtype(dy.dtype))
     return out
 
 
@@ -438,9 +417,7 @@ def linear_pre_gelu(a: Tensor, w: Tensor, bias: Tensor) -> Tuple[Tensor, Tensor]
     N = w.shape[0]
     pre = torch.empty((M, N), dtype=a.dtype, device=a.device)
     act = torch.empty_like(pre)
-    with torch.cuda.device(a.device):
-        _lib.check(_lib.load().uf_linear_pre_gelu_fwd(_ptr(a), _ptr(w), _ptr(_c(bias, torch.float32)), _ptr(pre), _ptr(act), M, N, K, uf_dtype(a.dtype), _stream()),
-                   "uf_linear_pre_gelu_fwd")
+    _launch("uf_linear_pre_gelu_fwd", a.device, a, w, _f32(bias), pre, act, M, N, K, uf_dtype(a.dtype))
     return pre, act
 
 
@@ -451,9 +428,7 @@ def linear_mul_dgelu(dy: Tensor, w_t: Tensor, zero_bias: Tensor, pre: Tensor) ->
     M, K = dy.shape
     N = w_t.shape[0]
     out = torch.empty((M, N), dtype=dy.dtype, device=dy.device)
-    with torch.cuda.device(dy.device):
-        _lib.check(_lib.load().uf_linear_mul_dgelu(_ptr(dy), _ptr(w_t), _ptr(_c(zero_bias, torch.float32)), _ptr(pre), _ptr(out), M, N, K, uf_dtype(dy.dtype), _stream()),
-                   "uf_linear_mul_dgelu")
+    _launch("uf_linear_mul_dgelu", dy.device, dy, w_t, _f32(zero_bias), pre, out, M, N, K, uf_dtype(dy.dtype))
     return out
 
 
@@ -463,8 +438,7 @@ def gelu(a: Tensor) -> Tensor:
     dt = uf_dtype(a.dtype)
     a = _c(a)
     out = torch.empty_like(a)
-    with torch.cuda.device(a.device):
-        _lib.check(_lib.load().uf_gelu_fwd(_ptr(a), _ptr(out), a.numel(), dt, _stream()), "uf_gelu_fwd")
+    _launch("uf_gelu_fwd", a.device, a, out, a.numel(), dt)
     return out
 
 
@@ -474,8 +448,7 @@ def gelu_bwd(a: Tensor, dy: Tensor) -> Tensor:
     dt = uf_dtype(a.dtype)
     a, dy = _c(a), _c(dy, a.dtype)
     out = torch.empty_like(a)
-    with torch.cuda.device(a.device):
-        _lib.check(_lib.load().uf_gelu_bwd(_ptr(a), _ptr(dy), _ptr(out), a.numel(), dt, _stream()), "uf_gelu_bwd")
+    _launch("uf_gelu_bwd", a.device, a, dy, out, a.numel(), dt)
     return out
 
 
@@ -488,12 +461,8 @@ def layernorm_bwd(x: Tensor, gamma: Tensor, dy: Tensor):
     dx = torch.empty_like(x2)
     dg = torch.empty(Cc, dtype=torch.float32, device=x.device)
     db = torch.empty(Cc, dtype=torch.float32, device=x.device)
-    lib = _lib.load()
-    nbytes = lib.uf_layernorm_bwd_workspace_bytes(rows, Cc)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.uf_layernorm_bwd(_ptr(x2), Cc, _ptr(_c(gamma, torch.float32)), _ptr(dy2), Cc, _ptr(dx), Cc, _ptr(dg), _ptr(db),
-                                        rows, Cc, _ptr(ws), nbytes, _stream()), "uf_layernorm_bwd")
+    _launch("uf_layernorm_bwd", x.device, x2, Cc, _f32(gamma), dy2, Cc, dx, Cc, dg, db, rows, Cc,
+            *_workspace("uf_layernorm_bwd_workspace_bytes", x.device, rows, Cc))
     return dx.reshape(x.shape), dg, db
 
 
@@ -510,22 +479,13 @@ def layernorm_bwd_fused(x: Tensor, gamma: Tensor, dy: Tensor, B: int, H: int, W:
     dx = torch.empty_like(x2)
     dg = torch.empty(Cc, dtype=torch.float32, device=x.device)
     db = torch.empty(Cc, dtype=torch.float32, device=x.device)
-    lib = _lib.load()
-    nbytes = lib.uf_layernorm_bwd_workspace_bytes(x2.shape[0], Cc)
-    ws = _ws(nbytes, x.device)
-    with torch.cuda.device(x.device):
-        if cast is None:
-            _lib.check(lib.uf_layernorm_bwd_fused(_ptr(x2), Cc, _ptr(_c(gamma, torch.float32)), _ptr(dy2), Cc, int(dy2.dtype == torch.float32), _ptr(add2), _ptr(dx), Cc,
-                                                  _ptr(dg), _ptr(db), B, H, W, Cc, int(windowed), shift, uf_dtype(dy2.dtype), _ptr(ws), nbytes, _stream()),
-                       "uf_layernorm_bwd_fused")
-            return dx, dg, db
-        out = torch.empty(B * H * W, Cc, dtype=dy2.dtype, device=x.device)
-        scale = cast.get("scale")
-        scale = None if scale is None else _c(scale, torch.float32)
-        _lib.check(lib.uf_layernorm_bwd_cast(_ptr(x2), Cc, _ptr(_c(gamma, torch.float32)), _ptr(dy2), Cc, int(dy2.dtype == torch.float32), _ptr(add2), _ptr(dx), Cc,
-                                             _ptr(dg), _ptr(db), B, H, W, Cc, int(windowed), shift, uf_dtype(dy2.dtype), _ptr(out), _ptr(scale),
-                                             int(bool(cast.get("windowed", False))), int(cast.get("shift", 0)), _ptr(ws), nbytes, _stream()),
-                   "uf_layernorm_bwd_cast")
+    ws = _workspace("uf_layernorm_bwd_workspace_bytes", x.device, x2.shape[0], Cc)
+    common = (x2, Cc, _f32(gamma), dy2, Cc, int(dy2.dtype == torch.float32), add2, dx, Cc, dg, db, B, H, W, Cc, int(windowed), shift, uf_dtype(dy2.dtype))
+    if cast is None:
+        _launch("uf_layernorm_bwd_fused", x.device, *common, *ws)
+        return dx, dg, db
+    out = torch.empty(B * H * W, Cc, dtype=dy2.dtype, device=x.device)
+    _launch("uf_layernorm_bwd_cast", x.device, *common, out, _f32(cast.get("scale")), int(bool(cast.get("windowed", False))), int(cast.get("shift", 0)), *ws)
     return dx, dg, db, out
 
 
@@ -539,12 +499,7 @@ def linear_wgrad(dy: Tensor, x: Tensor, with_bias: bool = True):
     M = x2.shape[0]
     dW = torch.empty(N, K, dtype=torch.float32, device=x.device)
     db = torch.empty(N, dtype=torch.float32, device=x.device) if with_bias else None
-    lib = _lib.load()
-    nbytes = lib.uf_linear_wgrad_workspace_bytes(M, N, K)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.uf_linear_wgrad(_ptr(dy2), N, _ptr(x2), K, _ptr(dW), _ptr(db) if db is not None else None, M, N, K, dt,
-                                       _ptr(ws), nbytes, _stream()), "uf_linear_wgrad")
+    _launch("uf_linear_wgrad", x.device, dy2, N, x2, K, dW, db, M, N, K, dt, *_workspace("uf_linear_wgrad_workspace_bytes", x.device, M, N, K))
     return dW, db
 
 
@@ -560,15 +515,9 @@ def window_attention_bwd(q: Tensor, k: Tensor, vt: Tensor, bias: Tensor, do: Ten
     n_windows = q.numel() // (heads * 64 * hd)           # q may be (nW*heads, 64, hd) or (nW, heads, 64, hd)
     dq, dk, dvt = torch.empty_like(q), torch.empty_like(k), torch.empty_like(vt)
     dbias = torch.empty(heads, 64, 64, dtype=torch.float32, device=q.device)
-    m = _c(mask, torch.float32) if mask is not None else None
-    lib = _lib.load()
-    nbytes = lib.uf_window_attention_bwd_workspace_bytes(n_windows, heads)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)
-    with torch.cuda.device(q.device):
-        _lib.check(lib.uf_window_attention_bwd(_ptr(q), _ptr(k), _ptr(vt), _ptr(_c(bias, torch.float32)), _ptr(m) if m is not None else None,
-                                               m.shape[0] if m is not None else 0, _ptr(do), do.shape[-1], _ptr(dq), _ptr(dk), _ptr(dvt),
-                                               _ptr(dbias), n_windows, heads, hd, H, W, shift, dt, _ptr(ws), nbytes, _stream()),
-                   "uf_window_attention_bwd")
+    m = _f32(mask)
+    _launch("uf_window_attention_bwd", q.device, q, k, vt, _f32(bias), m, m.shape[0] if m is not None else 0, do, do.shape[-1], dq, dk, dvt, dbias,
+            n_windows, heads, hd, H, W, shift, dt, *_workspace("uf_window_attention_bwd_workspace_bytes", q.device, n_windows, heads))
     return dq, dk, dvt, dbias
 
 
@@ -583,14 +532,9 @@ def window_attention_bwd_qkv(q: Tensor, k: Tensor, vt: Tensor, bias: Tensor, do:
     n_windows = q.numel() // (heads * 64 * hd)
     dqkv = torch.empty(n_windows * 64, 3 * heads * hd, dtype=q.dtype, device=q.device)
     dbias = torch.empty(heads, 64, 64, dtype=torch.float32, device=q.device)
-    m = _c(mask, torch.float32) if mask is not None else None
-    lib = _lib.load()
-    nbytes = lib.uf_window_attention_bwd_workspace_bytes(n_windows, heads)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)
-    with torch.cuda.device(q.device):
-        _lib.check(lib.uf_window_attention_bwd_qkv(_ptr(q), _ptr(k), _ptr(vt), _ptr(_c(bias, torch.float32)), _ptr(m) if m is not None else None,
-                                                   m.shape[0] if m is not None else 0, _ptr(do), do.shape[-1], _ptr(dqkv), _ptr(dbias), n_windows, heads, hd,
-                                                   H, W, shift, dt, _ptr(ws), nbytes, _stream()), "uf_window_attention_bwd_qkv")
+    m = _f32(mask)
+    _launch("uf_window_attention_bwd_qkv", q.device, q, k, vt, _f32(bias), m, m.shape[0] if m is not None else 0, do, do.shape[-1], dqkv, dbias,
+            n_windows, heads, hd, H, W, shift, dt, *_workspace("uf_window_attention_bwd_workspace_bytes", q.device, n_windows, heads))
     return dqkv, dbias
 
 
@@ -602,12 +546,7 @@ def dwconv3x3_wgrad(h: Tensor, dc: Tensor):
     B, H, W, Cc = h.shape
     dw9 = torch.empty(9, Cc, dtype=torch.float32, device=h.device)
     db = torch.empty(Cc, dtype=torch.float32, device=h.device)
-    lib = _lib.load()
-    nbytes = lib.uf_dwconv3x3_wgrad_workspace_bytes(Cc, dt)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=h.device)
-    with torch.cuda.device(h.device):
-        _lib.check(lib.uf_dwconv3x3_wgrad(_ptr(h), _ptr(dc), _ptr(dw9), _ptr(db), B, H, W, Cc, dt, _ptr(ws), nbytes, _stream()),
-                   "uf_dwconv3x3_wgrad")
+    _launch("uf_dwconv3x3_wgrad", h.device, h, dc, dw9, db, B, H, W, Cc, dt, *_workspace("uf_dwconv3x3_wgrad_workspace_bytes", h.device, Cc, dt))
     return dw9, db
 
 
@@ -621,12 +560,8 @@ def dwconv3x3_bwd(dc: Tensor, w9_flipped: Tensor, pre: Tensor):
     da = torch.empty_like(dc)
     dw9 = torch.empty(9, Cc, dtype=torch.float32, device=dc.device)
     db = torch.empty(Cc, dtype=torch.float32, device=dc.device)
-    lib = _lib.load()
-    nbytes = lib.uf_dwconv3x3_bwd_workspace_bytes(Cc, dt)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dc.device)
-    with torch.cuda.device(dc.device):
-        _lib.check(lib.uf_dwconv3x3_bwd(_ptr(dc), _ptr(_c(w9_flipped, torch.float32)), _ptr(pre), _ptr(da), _ptr(dw9), _ptr(db), B, H, W, Cc, dt,
-                                        _ptr(ws), nbytes, _stream()), "uf_dwconv3x3_bwd")
+    _launch("uf_dwconv3x3_bwd", dc.device, dc, _f32(w9_flipped), pre, da, dw9, db, B, H, W, Cc, dt,
+            *_workspace("uf_dwconv3x3_bwd_workspace_bytes", dc.device, Cc, dt))
     return da, dw9, db
 
 
@@ -638,10 +573,7 @@ def dwconv_linear2(h1: Tensor, w9: Tensor, bdw: Tensor, w2: Tensor, b2: Tensor, 
     B, H, W, hid = h1.shape
     out = _c(x, torch.float32).clone()
     Cc = out.shape[-1]
-    with torch.cuda.device(h1.device):
-        _lib.check(_lib.load().uf_dwconv_linear2_fwd(_ptr(h1), _ptr(_c(w9, torch.float32)), _ptr(_c(bdw, torch.float32)),
-                                                     _ptr(_pack_frag(_c(w2, h1.dtype))), _ptr(_c(b2, torch.float32)), _ptr(out), Cc, B, H, W, Cc,
-                                                     dt, _stream()), "uf_dwconv_linear2_fwd")
+    _launch("uf_dwconv_linear2_fwd", h1.device, h1, _f32(w9), _f32(bdw), _pack_frag(_c(w2, h1.dtype)), _f32(b2), out, Cc, B, H, W, Cc, dt)
     return out
 
 
@@ -660,10 +592,7 @@ def lewin_attn_train_fwd(bp, x: Tensor, B: int, H: int, W: int, heads: int, dtyp
     k = torch.empty_like(q)
     vt = torch.empty((M // 64, heads, hd, 64), dtype=T, device=dev)
     a1 = torch.empty((M, 4 * Cc), dtype=T, device=dev)
-    da = None if drop_attn is None else _c(drop_attn, torch.float32)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().uf_lewin_attn_train_fwd(bp, _ptr(x), Cc, _ptr(x1), Cc, B, H, W, Cc, _ptr(da), uf_dtype(dtype), _ptr(xn), _ptr(q), _ptr(k), _ptr(vt),
-                                                       _ptr(o), _ptr(z), _ptr(a1), _stream()), "uf_lewin_attn_train_fwd")
+    _launch("uf_lewin_attn_train_fwd", dev, bp, x, Cc, x1, Cc, B, H, W, Cc, _f32(drop_attn), uf_dtype(dtype), xn, q, k, vt, o, z, a1)
     return x1, xn, q, k, vt, o, z, a1
 
 
@@ -679,13 +608,10 @@ def downsample(x: Tensor, w_packed: Tensor, bias: Tensor, B: int, H: int, W: int
     x = _c(x, torch.float32)
     Cc = x.shape[-1]
     out = torch.empty((B * (H // 2) * (W // 2), 2 * Cc), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        if w_fm is not None:
-            _lib.check(_lib.load().uf_downsample_fm_fwd(_ptr(x), Cc, _ptr(_c(w_packed)), _ptr(_c(w_fm)), _ptr(_c(bias, torch.float32)), _ptr(out),
-                                                        2 * Cc, B, H, W, Cc, uf_dtype(w_packed.dtype), _stream()), "uf_downsample_fm_fwd")
-        else:
-            _lib.check(_lib.load().uf_downsample_fwd(_ptr(x), Cc, _ptr(_c(w_packed)), _ptr(_c(bias, torch.float32)), _ptr(out),
-                                                     2 * Cc, B, H, W, Cc, uf_dtype(w_packed.dtype), _stream()), "uf_downsample_fwd")
+    if w_fm is not None:
+        _launch("uf_downsample_fm_fwd", x.device, x, Cc, _c(w_packed), _c(w_fm), _f32(bias), out, 2 * Cc, B, H, W, Cc, uf_dtype(w_packed.dtype))
+    else:
+        _launch("uf_downsample_fwd", x.device, x, Cc, _c(w_packed), _f32(bias), out, 2 * Cc, B, H, W, Cc, uf_dtype(w_packed.dtype))
     return out
 
 
@@ -699,9 +625,7 @@ def upsample(x: Tensor, w_packed: Tensor, bias: Tensor, B: int, H: int, W: int, 
     if out is None:
         out = torch.empty((B * 4 * H * W, Cout), dtype=torch.float32, device=x.device)
         ld_o = Cout
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().uf_upsample_fwd(_ptr(x), Cin, _ptr(_c(w_packed)), _ptr(_c(bias, torch.float32)), _ptr(out), ld_o,
-                                               B, H, W, Cin, Cout, uf_dtype(w_packed.dtype), _stream()), "uf_upsample_fwd")
+    _launch("uf_upsample_fwd", x.device, x, Cin, _c(w_packed), _f32(bias), out, ld_o, B, H, W, Cin, Cout, uf_dtype(w_packed.dtype))
     return out
 
 
@@ -712,9 +636,7 @@ def input_proj(img: Tensor, w27: Tensor, bias: Tensor) -> Tensor:
     B, Cin, H, W = img.shape
     E = w27.shape[1]
     out = torch.empty((B * H * W, E), dtype=torch.float32, device=img.device)
-    with torch.cuda.device(img.device):
-        _lib.check(_lib.load().uf_input_proj_fwd(_ptr(img), _ptr(_c(w27, torch.float32)), _ptr(_c(bias, torch.float32)),
-                                                 _ptr(out), E, B, Cin, H, W, E, _stream()), "uf_input_proj_fwd")
+    _launch("uf_input_proj_fwd", img.device, img, _f32(w27), _f32(bias), out, E, B, Cin, H, W, E)
     return out
 
 
@@ -732,25 +654,13 @@ def output_proj(x: Tensor, w: Tensor, bias: Tensor, B: int, H: int, W: int, img:
         if tuple(img.shape) != (B, Cout, H, W):
             raise UformerHipError(f"output_proj: img {tuple(img.shape)} must have the output's shape {(B, Cout, H, W)}")
     out = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().uf_output_proj_c_fwd(_ptr(x), C2, _ptr(_c(w, torch.float32)), _ptr(_c(bias, torch.float32)),
-                                                    _ptr(img), _ptr(out), B, H, W, C2, Cout, int(img is not None), _stream()),
-                   "uf_output_proj_c_fwd")
+    _launch("uf_output_proj_c_fwd", x.device, x, C2, _f32(w), _f32(bias), img, out, B, H, W, C2, Cout, int(img is not None))
     return out
 
 
 # ---------------------------------------------------------------------------------------
 # training-step tail, metrics, arbitrary-resolution wrapper, input pipeline
 # ---------------------------------------------------------------------------------------
-def _byref(struct):
-    import ctypes
-    return ctypes.byref(struct)
-
-
-def _ws(nbytes: int, device) -> Tensor:
-    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
-
-
 def charbonnier(y: Tensor, target: Tensor, eps: float = 1e-3, with_grad: bool = True, grad_scale: float = 1.0):
     """CharbonnierLoss.forward (losses.py:41-52) and d loss / d y in ONE pass: returns (loss f32 0-dim tensor, dy or None)."""
     _dev(y, target)
@@ -758,19 +668,13 @@ def charbonnier(y: Tensor, target: Tensor, eps: float = 1e-3, with_grad: bool = 
     n = y.numel()
     loss = torch.empty(1, dtype=torch.float32, device=y.device)
     dy = torch.empty_like(y) if with_grad else None
-    lib = _lib.load()
-    nbytes = lib.uf_charbonnier_workspace_bytes(n)
-    ws = _ws(nbytes, y.device)
-    with torch.cuda.device(y.device):
-        _lib.check(lib.uf_charbonnier_fwd_bwd(_ptr(y), _ptr(target), _ptr(dy), _ptr(loss), n, eps, grad_scale, _ptr(ws), nbytes, _stream()),
-                   "uf_charbonnier_fwd_bwd")
+    _launch("uf_charbonnier_fwd_bwd", y.device, y, target, dy, loss, n, eps, grad_scale, *_workspace("uf_charbonnier_workspace_bytes", y.device, n))
     return loss.reshape(()), dy
 
 
 def adamw_step(params, grads, exp_avg, exp_avg_sq, *, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.02,
                step: int = 1, grad_scale: float = 1.0) -> None:
     """One torch.optim.AdamW step over lists of f32 tensors, in place (train/train_denoise.py:77).  ``step`` counts from 1."""
-    import ctypes as C
     n = len(params)
     if not (len(grads) == len(exp_avg) == len(exp_avg_sq) == n):
         raise UformerHipError("adamw_step: list lengths differ")
@@ -781,18 +685,16 @@ def adamw_step(params, grads, exp_avg, exp_avg_sq, *, lr: float, betas=(0.9, 0.9
         for t in group:
             if t.dtype != torch.float32 or not t.is_contiguous():
                 raise UformerHipError("adamw_step: tensors must be contiguous float32")
-    arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])      # noqa: E731
-    numel = (C.c_longlong * n)(*[p.numel() for p in params])
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().uf_adamw_step(arr(params), arr(grads), arr(exp_avg), arr(exp_avg_sq), numel, n, lr, betas[0], betas[1], eps,
-                                             weight_decay, int(step), grad_scale, _stream()), "uf_adamw_step")
+    arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])      # noqa: E731
+    numel = (ctypes.c_longlong * n)(*[p.numel() for p in params])
+    _launch("uf_adamw_step", dev, arr(params), arr(grads), arr(exp_avg), arr(exp_avg_sq), numel, n, lr, betas[0], betas[1], eps,
+            weight_decay, int(step), grad_scale)
 
 
 def adamw_step_scaled(params, grads, exp_avg, exp_avg_sq, scaler_state: Tensor, *, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.02,
                       grad_scale: float = 1.0) -> None:
     """``adamw_step`` under a device-resident dynamic loss scale (uf_adamw_step_scaled): gradients x grad_scale / scale, nothing written when
     ``scaler_state[2]`` (found_inf) is set, bias corrections at step ``scaler_state[4] + 1``.  No host synchronisation."""
-    import ctypes as C
     n = len(params)
     if not (len(grads) == len(exp_avg) == len(exp_avg_sq) == n):
         raise UformerHipError("adamw_step_scaled: list lengths differ")
@@ -803,16 +705,14 @@ def adamw_step_scaled(params, grads, exp_avg, exp_avg_sq, scaler_state: Tensor, 
         for t in group:
             if t.dtype != torch.float32 or not t.is_contiguous():
                 raise UformerHipError("adamw_step_scaled: tensors must be contiguous float32")
-    arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])      # noqa: E731
-    numel = (C.c_longlong * n)(*[p.numel() for p in params])
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().uf_adamw_step_scaled(arr(params), arr(grads), arr(exp_avg), arr(exp_avg_sq), numel, n, lr, betas[0], betas[1], eps,
-                                                    weight_decay, grad_scale, _ptr(scaler_state), _stream()), "uf_adamw_step_scaled")
+    arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])      # noqa: E731
+    numel = (ctypes.c_longlong * n)(*[p.numel() for p in params])
+    _launch("uf_adamw_step_scaled", dev, arr(params), arr(grads), arr(exp_avg), arr(exp_avg_sq), numel, n, lr, betas[0], betas[1], eps,
+            weight_decay, grad_scale, scaler_state)
 
 
 def grad_scaler_check(grads, scaler_state: Tensor) -> None:
     """scaler_state[2] = 1 if any gradient element is inf / nan (uf_grad_scaler_check)."""
-    import ctypes as C
     grads = [g for g in grads if g is not None]
     n = len(grads)
     if n == 0:
@@ -821,17 +721,15 @@ def grad_scaler_check(grads, scaler_state: Tensor) -> None:
     for t in grads:
         if t.dtype != torch.float32 or not t.is_contiguous():
             raise UformerHipError("grad_scaler_check: gradients must be contiguous float32")
-    arr = (C.c_void_p * n)(*[t.data_ptr() for t in grads])
-    numel = (C.c_longlong * n)(*[t.numel() for t in grads])
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().uf_grad_scaler_check(arr, numel, n, _ptr(scaler_state), _stream()), "uf_grad_scaler_check")
+    arr = (ctypes.c_void_p * n)(*[t.data_ptr() for t in grads])
+    numel = (ctypes.c_longlong * n)(*[t.numel() for t in grads])
+    _launch("uf_grad_scaler_check", dev, arr, numel, n, scaler_state)
 
 
 def grad_scaler_update(scaler_state: Tensor, growth_factor: float = 2.0, backoff_factor: float = 0.5, growth_interval: int = 2000) -> None:
     """GradScaler.update() on the device (uf_grad_scaler_update)."""
     _dev(scaler_state)
-    with torch.cuda.device(scaler_state.device):
-        _lib.check(_lib.load().uf_grad_scaler_update(_ptr(scaler_state), growth_factor, backoff_factor, int(growth_interval), _stream()), "uf_grad_scaler_update")
+    _launch("uf_grad_scaler_update", scaler_state.device, scaler_state, growth_factor, backoff_factor, int(growth_interval))
 
 
 def batch_mse(a: Tensor, b: Tensor, clamp01: bool = True) -> Tensor:
@@ -842,11 +740,7 @@ def batch_mse(a: Tensor, b: Tensor, clamp01: bool = True) -> Tensor:
         raise UformerHipError(f"batch_mse: shapes {tuple(a.shape)} / {tuple(b.shape)}")
     B, Cc, H, W = a.shape
     out = torch.empty(B, dtype=torch.float32, device=a.device)
-    lib = _lib.load()
-    nbytes = lib.uf_image_metric_workspace_bytes(B, Cc, H, W)
-    ws = _ws(nbytes, a.device)
-    with torch.cuda.device(a.device):
-        _lib.check(lib.uf_batch_mse(_ptr(a), _ptr(b), _ptr(out), B, Cc, H, W, int(clamp01), _ptr(ws), nbytes, _stream()), "uf_batch_mse")
+    _launch("uf_batch_mse", a.device, a, b, out, B, Cc, H, W, int(clamp01), *_workspace("uf_image_metric_workspace_bytes", a.device, B, Cc, H, W))
     return out
 
 
@@ -858,11 +752,7 @@ def batch_ssim(a: Tensor, b: Tensor) -> Tensor:
         raise UformerHipError(f"batch_ssim: shapes {tuple(a.shape)} / {tuple(b.shape)}")
     B, Cc, H, W = a.shape
     out = torch.empty(B, dtype=torch.float32, device=a.device)
-    lib = _lib.load()
-    nbytes = lib.uf_image_metric_workspace_bytes(B, Cc, H, W)
-    ws = _ws(nbytes, a.device)
-    with torch.cuda.device(a.device):
-        _lib.check(lib.uf_batch_ssim(_ptr(a), _ptr(b), _ptr(out), B, Cc, H, W, _ptr(ws), nbytes, _stream()), "uf_batch_ssim")
+    _launch("uf_batch_ssim", a.device, a, b, out, B, Cc, H, W, *_workspace("uf_image_metric_workspace_bytes", a.device, B, Cc, H, W))
     return out
 
 
@@ -875,8 +765,7 @@ def expand2square(img: Tensor, factor: float = 128.0, with_mask: bool = True):
     X = int(math.ceil(max(h, w) / float(factor)) * factor)
     canvas = torch.empty((B, Cc, X, X), dtype=torch.float32, device=img.device)
     mask = torch.empty((B, 1, X, X), dtype=torch.float32, device=img.device) if with_mask else None
-    with torch.cuda.device(img.device):
-        _lib.check(_lib.load().uf_expand2square(_ptr(img), _ptr(canvas), _ptr(mask), B, Cc, h, w, X, _stream()), "uf_expand2square")
+    _launch("uf_expand2square", img.device, img, canvas, mask, B, Cc, h, w, X)
     return canvas, mask
 
 
@@ -888,8 +777,7 @@ def crop_clamp(canvas: Tensor, h: int, w: int, clamp: bool = True) -> Tensor:
     if X != X2:
         raise UformerHipError("crop_clamp: square canvas expected")
     out = torch.empty((B, Cc, h, w), dtype=torch.float32, device=canvas.device)
-    with torch.cuda.device(canvas.device):
-        _lib.check(_lib.load().uf_crop_clamp(_ptr(canvas), _ptr(out), B, Cc, h, w, X, int(clamp), _stream()), "uf_crop_clamp")
+    _launch("uf_crop_clamp", canvas.device, canvas, out, B, Cc, h, w, X, int(clamp))
     return out
 
 
@@ -903,8 +791,7 @@ def expand_canvas(img: Tensor, Xh: int, Xw: int, with_mask: bool = True):
         raise UformerHipError(f"expand_canvas: canvas {Xh}x{Xw} smaller than the image {h}x{w}")
     canvas = torch.empty((B, Cc, Xh, Xw), dtype=torch.float32, device=img.device)
     mask = torch.empty((B, 1, Xh, Xw), dtype=torch.float32, device=img.device) if with_mask else None
-    with torch.cuda.device(img.device):
-        _lib.check(_lib.load().uf_expand_canvas(_ptr(img), _ptr(canvas), _ptr(mask), B, Cc, h, w, Xh, Xw, _stream()), "uf_expand_canvas")
+    _launch("uf_expand_canvas", img.device, img, canvas, mask, B, Cc, h, w, Xh, Xw)
     return canvas, mask
 
 
@@ -914,8 +801,7 @@ def crop_clamp_canvas(canvas: Tensor, h: int, w: int, clamp: bool = True) -> Ten
     canvas = _c(canvas, torch.float32)
     B, Cc, Xh, Xw = canvas.shape
     out = torch.empty((B, Cc, h, w), dtype=torch.float32, device=canvas.device)
-    with torch.cuda.device(canvas.device):
-        _lib.check(_lib.load().uf_crop_clamp_canvas(_ptr(canvas), _ptr(out), B, Cc, h, w, Xh, Xw, int(clamp), _stream()), "uf_crop_clamp_canvas")
+    _launch("uf_crop_clamp_canvas", canvas.device, canvas, out, B, Cc, h, w, Xh, Xw, int(clamp))
     return out
 
 
@@ -932,9 +818,7 @@ def crop_augment(frames: Tensor, meta: Tensor, ps: int, hwc: bool = False) -> Te
     H, W, Cc = (frames.shape[1], frames.shape[2], frames.shape[3]) if hwc else (frames.shape[2], frames.shape[3], frames.shape[1])
     B = meta.shape[0]
     out = torch.empty((B, Cc, ps, ps), dtype=torch.float32, device=frames.device)
-    with torch.cuda.device(frames.device):
-        _lib.check(_lib.load().uf_crop_augment_c(_ptr(frames), int(frames.dtype == torch.uint8), int(hwc), _ptr(out), _ptr(meta), B, N, Cc, H, W, ps,
-                                                 _stream()), "uf_crop_augment_c")
+    _launch("uf_crop_augment_c", frames.device, frames, int(frames.dtype == torch.uint8), int(hwc), out, meta, B, N, Cc, H, W, ps)
     return out
 
 
@@ -944,9 +828,7 @@ def mixup(x: Tensor, lam: Tensor, perm: Tensor) -> Tensor:
     x = _c(x, torch.float32)
     B = x.shape[0]
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().uf_mixup(_ptr(x), _ptr(out), _ptr(_c(lam.reshape(-1), torch.float32)), _ptr(_c(perm, torch.int32)), B,
-                                        x.numel() // B, _stream()), "uf_mixup")
+    _launch("uf_mixup", x.device, x, out, _f32(lam.reshape(-1)), _c(perm, torch.int32), B, x.numel() // B)
     return out
 
 
@@ -960,11 +842,7 @@ def rows_sum(x: Tensor) -> Tensor:
     x = _c(x)
     M, N = x.shape
     out = torch.empty(N, dtype=torch.float32, device=x.device)
-    lib = _lib.load()
-    nbytes = lib.uf_rows_sum_workspace_bytes(M, N)
-    ws = _ws(nbytes, x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.uf_rows_sum(_ptr(x), N, _ptr(out), M, N, dt, _ptr(ws), nbytes, _stream()), "uf_rows_sum")
+    _launch("uf_rows_sum", x.device, x, N, out, M, N, dt, *_workspace("uf_rows_sum_workspace_bytes", x.device, M, N))
     return out
 
 
@@ -1003,23 +881,20 @@ def lewin_block_bwd(tp, x: Tensor, dy: Tensor, drop_attn: Optional[Tensor], drop
     _dev(x, dy)
     x, dy = _c(x, torch.float32), _c(dy, torch.float32)
     C = x.shape[-1]
-    lib = _lib.load()
     dt = uf_dtype(dtype)
-    nbytes = lib.uf_lewin_block_bwd_workspace_bytes(B, H, W, C, heads, dt)
+    nbytes = _lib.load().uf_lewin_block_bwd_workspace_bytes(B, H, W, C, heads, dt)
     if ws is None or ws.numel() < nbytes:
         ws = _ws(nbytes, x.device)
     _flat, g, views = _block_grads(C, heads, bool(tp.modulator), x.device)
     dx = torch.empty_like(x)
-    da = None if drop_attn is None else _c(drop_attn, torch.float32)
-    dl = None if drop_leff is None else _c(drop_leff, torch.float32)
-    with torch.cuda.device(x.device):
-        if half == "block":
-            rc = lib.uf_lewin_block_bwd(_byref(tp), _ptr(x), _ptr(dy), _ptr(dx), _ptr(da), _ptr(dl), _byref(g), B, H, W, C, dt, _ptr(ws), ws.numel(), _stream())
-        elif half == "leff":
-            rc = lib.uf_leff_bwd(_byref(tp), _ptr(x), _ptr(dy), _ptr(dx), _ptr(dl), _byref(g), B, H, W, C, dt, _ptr(ws), ws.numel(), _stream())
-        else:
-            rc = lib.uf_lewin_attn_bwd(_byref(tp), _ptr(x), _ptr(dy), _ptr(dx), _ptr(da), _byref(g), B, H, W, C, dt, _ptr(ws), ws.numel(), _stream())
-        _lib.check(rc, "uf_lewin_block_bwd" if half == "block" else ("uf_leff_bwd" if half == "leff" else "uf_lewin_attn_bwd"))
+    da, dl = _f32(drop_attn), _f32(drop_leff)
+    if half == "block":
+        name, drops = "uf_lewin_block_bwd", (da, dl)
+    elif half == "leff":
+        name, drops = "uf_leff_bwd", (dl,)
+    else:
+        name, drops = "uf_lewin_attn_bwd", (da,)
+    _launch(name, x.device, ctypes.byref(tp), x, dy, dx, *drops, ctypes.byref(g), B, H, W, C, dt, ws, ws.numel())
     if half != "block":       # a half writes only its own parameters' gradients: never hand out the other half's uninitialised views
         mine = {"leff": ("norm2_w", "norm2_b", "w1", "b1", "wdw", "bdw", "w2", "b2"),
                 "attn": ("norm1_w", "norm1_b", "modulator", "rpb_table", "wqkv", "bqkv", "wproj", "bproj")}[half]
@@ -1039,12 +914,8 @@ def downsample_bwd(x: Tensor, dy: Tensor, w_pk_t: Tensor, B: int, H: int, W: int
     dx = add_to if add_to is not None else torch.empty(B * H * W, Cin, dtype=torch.float32, device=x.device)
     dW = torch.empty(Cout, 16 * Cin, dtype=torch.float32, device=x.device)
     db = torch.empty(Cout, dtype=torch.float32, device=x.device)
-    lib = _lib.load()
-    nbytes = lib.uf_downsample_bwd_workspace_bytes(B, H, W, Cin, Cout, dt)
-    ws = _ws(nbytes, x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.uf_downsample_bwd(_ptr(x), x.stride(0), _ptr(dy), _ptr(_c(w_pk_t)), _ptr(dx), dx.stride(0), int(add_to is not None), _ptr(dW), _ptr(db),
-                                         B, H, W, Cin, Cout, dt, _ptr(ws), nbytes, _stream()), "uf_downsample_bwd")
+    _launch("uf_downsample_bwd", x.device, x, x.stride(0), dy, _c(w_pk_t), dx, dx.stride(0), int(add_to is not None), dW, db, B, H, W, Cin, Cout, dt,
+            *_workspace("uf_downsample_bwd_workspace_bytes", x.device, B, H, W, Cin, Cout, dt))
     return dx, dW, db
 
 
@@ -1060,12 +931,8 @@ def upsample_cat_bwd(d: Tensor, x: Tensor, w_pk_t: Tensor, B: int, H: int, W: in
     dx = torch.empty(B * H * W, Cin, dtype=torch.float32, device=x.device)
     dW = torch.empty(4 * Cout, Cin, dtype=torch.float32, device=x.device)
     db = torch.empty(Cout, dtype=torch.float32, device=x.device)
-    lib = _lib.load()
-    nbytes = lib.uf_upsample_cat_bwd_workspace_bytes(B, H, W, Cin, Cout, dt)
-    ws = _ws(nbytes, x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.uf_upsample_cat_bwd(_ptr(d), d.stride(0), _ptr(x), Cin, _ptr(_c(w_pk_t)), _ptr(dx), _ptr(dW), _ptr(db), B, H, W, Cin, Cout, dt,
-                                           _ptr(ws), nbytes, _stream()), "uf_upsample_cat_bwd")
+    _launch("uf_upsample_cat_bwd", x.device, d, d.stride(0), x, Cin, _c(w_pk_t), dx, dW, db, B, H, W, Cin, Cout, dt,
+            *_workspace("uf_upsample_cat_bwd_workspace_bytes", x.device, B, H, W, Cin, Cout, dt))
     return dx, dW, db
 
 
@@ -1076,15 +943,10 @@ def conv3x3_bwd(x: Tensor, dy_rows: Tensor, w: Tensor, B: int, H: int, W: int, n
     _dev(x, dy_rows, w)
     x, dy_rows, w = _c(x, torch.float32), _c(dy_rows, torch.float32), _c(w, torch.float32)
     Cout, Cin = w.shape[0], w.shape[1]
-    act_out = None if act_out is None else _c(act_out, torch.float32)
     dx = torch.empty_like(x) if need_dx else None
     dW, db = torch.empty_like(w), torch.empty(Cout, dtype=torch.float32, device=x.device)
-    lib = _lib.load()
-    nbytes = lib.uf_conv3x3_bwd_workspace_bytes(B, H, W, Cin, Cout)
-    ws = _ws(nbytes, x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.uf_conv3x3_bwd(_ptr(x), int(nchw), _ptr(dy_rows), _ptr(act_out), slope, _ptr(w), _ptr(dx), _ptr(dW), _ptr(db), B, H, W, Cin, Cout,
-                                      _ptr(ws), nbytes, _stream()), "uf_conv3x3_bwd")
+    _launch("uf_conv3x3_bwd", x.device, x, int(nchw), dy_rows, _f32(act_out), slope, w, dx, dW, db, B, H, W, Cin, Cout,
+            *_workspace("uf_conv3x3_bwd_workspace_bytes", x.device, B, H, W, Cin, Cout))
     return dx, dW, db
 
 
@@ -1095,11 +957,7 @@ def residual_combine(a: Optional[Tensor], b: Tensor, scale: Optional[Tensor], B:
     b = _c(b)
     C = b.shape[-1]
     out = torch.empty(B * H * W, C, dtype=torch.float32, device=b.device)
-    a = None if a is None else _c(a, torch.float32)
-    scale = None if scale is None else _c(scale, torch.float32)
-    with torch.cuda.device(b.device):
-        _lib.check(_lib.load().uf_residual_combine(_ptr(a), _ptr(b), int(b.dtype == torch.float32), _ptr(out), _ptr(scale), B, H, W, C, int(windowed), shift,
-                                                   uf_dtype(b.dtype), _stream()), "uf_residual_combine")
+    _launch("uf_residual_combine", b.device, _f32(a), b, int(b.dtype == torch.float32), out, _f32(scale), B, H, W, C, int(windowed), shift, uf_dtype(b.dtype))
     return out
 
 
@@ -1109,14 +967,10 @@ def grad_fork(g1: Tensor, g2: Optional[Tensor], scale: Optional[Tensor], B: int,
     when ``windowed``)."""
     _dev(g1)
     g1 = _c(g1, torch.float32)
-    g2 = None if g2 is None else _c(g2, torch.float32)
     C = g1.shape[-1]
-    scale = None if scale is None else _c(scale, torch.float32)
     tot = torch.empty_like(g1) if want_sum else None
     out = torch.empty(B * H * W, C, dtype=dtype, device=g1.device)
-    with torch.cuda.device(g1.device):
-        _lib.check(_lib.load().uf_grad_fork(_ptr(g1), _ptr(g2), _ptr(tot), _ptr(out), _ptr(scale), B, H, W, C, int(windowed), shift, uf_dtype(dtype), _stream()),
-                   "uf_grad_fork")
+    _launch("uf_grad_fork", g1.device, g1, _f32(g2), tot, out, _f32(scale), B, H, W, C, int(windowed), shift, uf_dtype(dtype))
     return tot, out
 
 
@@ -1127,8 +981,7 @@ def qkv_grad_merge(dq: Tensor, dk: Tensor, dvt: Tensor, heads: int) -> Tensor:
     hd = dq.shape[-1]
     nW = dq.numel() // (heads * 64 * hd)
     out = torch.empty(nW * 64, 3 * heads * hd, dtype=dq.dtype, device=dq.device)
-    with torch.cuda.device(dq.device):
-        _lib.check(_lib.load().uf_qkv_grad_merge(_ptr(dq), _ptr(dk), _ptr(dvt), _ptr(out), nW, heads, hd, uf_dtype(dq.dtype), _stream()), "uf_qkv_grad_merge")
+    _launch("uf_qkv_grad_merge", dq.device, dq, dk, dvt, out, nW, heads, hd, uf_dtype(dq.dtype))
     return out
 
 
@@ -1138,8 +991,7 @@ def rpb_table_grad(dbias: Tensor) -> Tensor:
     dbias = _c(dbias, torch.float32)
     heads = dbias.shape[0]
     out = torch.empty(225, heads, dtype=torch.float32, device=dbias.device)
-    with torch.cuda.device(dbias.device):
-        _lib.check(_lib.load().uf_rpb_table_grad(_ptr(dbias), _ptr(out), heads, _stream()), "uf_rpb_table_grad")
+    _launch("uf_rpb_table_grad", dbias.device, dbias, out, heads)
     return out
 
 
@@ -1152,8 +1004,7 @@ def im2col(x: Tensor, B: int, H: int, W: int, Cin: int, k: int, stride: int, pad
     ldc = (k * k * Cin + 7) // 8 * 8
     dt = uf_dtype(dtype)
     cols = torch.empty((B * Ho * Wo, ldc), dtype=torch_dtype(dt), device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().uf_im2col(_ptr(x), Cin, _ptr(cols), ldc, B, H, W, Cin, k, stride, pad, int(nchw), dt, _stream()), "uf_im2col")
+    _launch("uf_im2col", x.device, x, Cin, cols, ldc, B, H, W, Cin, k, stride, pad, int(nchw), dt)
     return cols
 
 
@@ -1167,9 +1018,7 @@ def col2im(dcols: Tensor, B: int, H: int, W: int, Cin: int, k: int, stride: int,
         out = torch.empty((B, Cin, H, W) if nchw else (B * H * W, Cin), dtype=torch.float32, device=dcols.device)
     elif not out.is_contiguous() or out.dtype != torch.float32:
         raise UformerHipError("col2im: out must be contiguous float32")
-    with torch.cuda.device(dcols.device):
-        _lib.check(_lib.load().uf_col2im(_ptr(dcols), dcols.shape[1], _ptr(out), Cin, B, H, W, Cin, k, stride, pad, int(nchw), int(acc), dt, _stream()),
-                   "uf_col2im")
+    _launch("uf_col2im", dcols.device, dcols, dcols.shape[1], out, Cin, B, H, W, Cin, k, stride, pad, int(nchw), int(acc), dt)
     return out
 
 
@@ -1180,12 +1029,6 @@ def lewin_block_train_fwd(bp, x: Tensor, B: int, H: int, W: int, dtype, drop_att
     dt = uf_dtype(dtype)
     y = _c(x, torch.float32).clone()
     Cc = y.shape[-1]
-    lib = _lib.load()
-    nbytes = lib.uf_block_workspace_bytes(B * H * W, Cc, dt)
-    ws = _ws(nbytes, y.device)
-    da = None if drop_attn is None else _c(drop_attn, torch.float32)
-    dl = None if drop_leff is None else _c(drop_leff, torch.float32)
-    with torch.cuda.device(y.device):
-        _lib.check(lib.uf_lewin_block_train_fwd(bp, _ptr(y), Cc, B, H, W, Cc, _ptr(da), _ptr(dl), dt, _ptr(ws), nbytes, _stream()),
-                   "uf_lewin_block_train_fwd")
+    _launch("uf_lewin_block_train_fwd", y.device, bp, y, Cc, B, H, W, Cc, _f32(drop_attn), _f32(drop_leff), dt,
+            *_workspace("uf_block_workspace_bytes", y.device, B * H * W, Cc, dt))
     return y

@@ -149,9 +149,8 @@ class NativeBlockPack:
         self._buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self.fused, self.train_params = _lib.BlockParams(), _lib.BlockTrainParams()
         import ctypes
-        with torch.cuda.device(dev):
-            _lib.check(lib.uf_pack_block_train(ctypes.byref(raw), C, heads, shift, dt, self._buf.data_ptr(), nbytes, ctypes.byref(self.fused),
-                                               ctypes.byref(self.train_params), torch.cuda.current_stream().cuda_stream), "uf_pack_block_train")
+        ops._launch("uf_pack_block_train", dev, ctypes.byref(raw), C, heads, shift, dt, self._buf, nbytes, ctypes.byref(self.fused),
+                    ctypes.byref(self.train_params))
         # the same operands as tensors (views into the pack buffer) for the op-by-op forward / backward: the BlockPack attributes
         tp, esz = self.train_params, torch.empty(0, dtype=T).element_size()
 
