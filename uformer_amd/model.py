@@ -585,6 +585,11 @@ class Uformer(nn.Module):
             raise NotImplementedError(f"img_size={img_size}: stage {STAGES[s_]} has resolution {res_}, so the reference would run it on "
                                       f"{win_}x{win_} windows; the HIP path is built for 8x8 windows and, for the bottleneck (conv) alone, 4x4 "
                                       f"(img_size // 16 == 4, e.g. 64)")
+        if win_size == 8 and self.cfg.stage_windows()[4] == 4 and (e16 := 16 * embed_dim) // num_heads[4] not in (16, 32):
+            # found by tests/test_gpu_switch_matrix.py: the form built and its first forward failed inside uf_uformer_win4_fwd
+            raise NotImplementedError(f"embed_dim={embed_dim} with img_size={img_size}: the bottleneck would run 4x4 windows at head_dim "
+                                      f"{e16 // num_heads[4]}, and the 4x4-window kernels (uf_win4.hip) are built for head_dim 16 and 32 "
+                                      f"(embed_dim 64 takes img_size 128 and up)")
         enc_dpr = [x.item() for x in torch.linspace(0, drop_path_rate, sum(depths[:self.num_enc_layers]))]
         conv_dpr = [drop_path_rate] * depths[4]
         dec_dpr = enc_dpr[::-1]
