@@ -554,6 +554,34 @@ int uf_crop_augment_c(const void* src, int src_is_u8, int src_hwc, float* out, c
  * device) is clamped into [0, B), as uf_crop_augment clamps its metadata. */
 int uf_mixup(const float* x, float* out, const float* lam, const int* perm, int B, long long per_sample, void* stream);
 
+/* ---- uint8 frames in and out of infer.restore / infer.restore_tiled on the device ---------------------------------
+ * Every caller starts and ends with uint8 pixels (load_img, utils/image_utils.py:31-35; img_as_ubyte(torch.clamp(restored, 0, 1)),
+ * test/test_gopro_hide.py:103-110).  All four validate before any launch: null pointers (UF_ERR_NULL); C outside its range or swap_rb with
+ * C < 3 (UF_ERR_UNSUPPORTED); a canvas smaller than the image, a tile that is no multiple of 128, element or byte counts of 2^31 and more
+ * (UF_ERR_SHAPE).  Rows of any length and alignment; swap_rb exchanges channels 0 and 2 (BGR / BGRA frames of a decoder).
+ *
+ * uf_frames_to_canvas: frames u8 (B,h,w,C) (hwc) or (B,C,h,w), dense, C = 1 ... 8 -> canvas f32 (B,C,Xh,Xw) = (float)u / 255.0f (IEEE division)
+ * at ((Xh-h)/2, (Xw-w)/2) and 0 elsewhere, mask (B,1,Xh,Xw) or NULL: uf_expand_canvas of the float frames bit for bit, one pass, no memset.
+ * uf_canvas_to_frames: the way back, C = 1 ... 4: q = rint(min(max(v, 0), 1) * 255.0f) of the same region, the product taken in f32, ties to
+ * even: img_as_ubyte(clamp(x, 0, 1)) for float32 input.  NaN gives 0 BY DEFINITION (skimage leaves it undefined); -0, negatives and -inf give
+ * 0, values above 1 and +inf give 255. */
+int uf_frames_to_canvas(const uint8_t* frames, int hwc, int swap_rb, float* canvas, float* mask, int B, int C, int h, int w, int Xh, int Xw,
+                        void* stream);
+int uf_canvas_to_frames(const float* canvas, uint8_t* frames, int hwc, int swap_rb, int B, int C, int h, int w, int Xh, int Xw, void* stream);
+/* uf_tiles_gather: the tile batch of infer.restore_tiled.  src: B frames, u8 (divided by 255) or f32, (B,h,w,C) or (B,C,h,w), C = 1 ... 8;
+ * origins: int32 [T][2] = {y, x} ON THE DEVICE; tiles f32 (T*B, C, tile, tile): entry k * B + b is frame b from origin k, zero beyond the
+ * frame (an origin outside the frame gives zeros; nothing outside the frames is read).
+ * uf_tiles_blend: out(y,x) = sum_t w_t o_t / sum_t w_t over ALL tiles t = (ty,tx) that cover the pixel, in f32 and ascending job order
+ * [(y,x) for y in ys for x in xs]; tiles_out f32 (ny*nx*B, C, tile, tile) in that order.  w_t = wy wx, each restore_tiled's ramp in closed
+ * form: 1 inside, (i + 0.5) / ov over the ov columns shared with the previous start, times 1 - (j + 0.5) / ov over those shared with the next.
+ * ys, xs: int32 arrays ON THE HOST (they travel as kernel arguments), at most 64 each, starting at 0, ascending by at most a tile and reaching
+ * the far side.  No atomics, no accumulator or weight-sum buffer.  out: f32 planes (B,C,h,w), C = 1 ... 8, clamped to [0,1] when clamp01
+ * (torch.clamp: NaN stays), or u8 frames (out_is_u8; (B,h,w,C) when out_hwc), C = 1 ... 4, through the quantiser of uf_canvas_to_frames. */
+int uf_tiles_gather(const void* src, int src_is_u8, int src_hwc, int swap_rb, float* tiles, const int* origins, int T, int B, int C, int h, int w,
+                    int tile, void* stream);
+int uf_tiles_blend(const float* tiles_out, const int* ys, int ny, const int* xs, int nx, void* out, int out_is_u8, int out_hwc, int swap_rb,
+                   int clamp01, int B, int C, int h, int w, int tile, void* stream);
+
 /* ---- cross-modulator attention of a decoder block (LeWinTransformerBlock(cross_modulator=True), model.py:873-877, :945-949; Attention :549-595;
  * LinearProjection.forward with attn_kv :431-442), one kernel, in place on the f32 stream:
  *   x[m] += proj( softmax_over_64_keys( q[m]_h K_h^T ) V_h ),   q[m] = (x[m] Wq^T + bq) hd^-0.5,   K | V = to_kv(cross_modulator.weight)

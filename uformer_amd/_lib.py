@@ -180,6 +180,10 @@ SIGNATURES = {
     "uf_crop_augment": (I, [P, I, I, P, P, I, I, I, I, I, P]),
     "uf_crop_augment_c": (I, [P, I, I, P, P, I, I, I, I, I, I, P]),
     "uf_mixup": (I, [P, P, P, P, I, C.c_longlong, P]),
+    "uf_frames_to_canvas": (I, [P, I, I, P, P, I, I, I, I, I, I, P]),
+    "uf_canvas_to_frames": (I, [P, P, I, I, I, I, I, I, I, I, P]),
+    "uf_tiles_gather": (I, [P, I, I, I, P, P, I, I, I, I, I, I, P]),
+    "uf_tiles_blend": (I, [P, P, I, P, I, P, I, I, I, I, I, I, I, I, I, P]),
     "uf_uformer_workspace_bytes": (c_size_t, [C.POINTER(ModelDesc), I, I, I, I]),
     "uf_uformer_fwd": (I, [C.POINTER(ModelDesc), P, P, I, I, I, I, P, c_size_t, P]),
     "uf_window4_attention_fwd": (I, [P, I, P, P, I, I, I, I, I, I, I, P]),

@@ -243,3 +243,195 @@ class PipelinedForward:
                 yield pending.pop(0).result()
         while pending:
             yield pending.pop(0).result()
+
+
+# ---------------------------------------------------------------------------------------
+# uint8 frames in, uint8 frames out
+# ---------------------------------------------------------------------------------------
+def _check_frames(frames, hwc: bool, bgr: bool, canvas: str, what: str):
+    """(B, C, h, w) of a uint8 frame batch, after the argument checks both frame interfaces share (they run before anything touches a device)"""
+    if canvas not in ("square", "rect"):
+        raise ValueError(f"{what}: canvas must be 'square' or 'rect', got {canvas!r}")
+    if frames.dtype != torch.uint8:
+        raise ValueError(f"{what}: frames must be uint8, got {frames.dtype}")
+    if frames.dim() != 4:
+        raise ValueError(f"{what}: frames must be (B,h,w,C) or (B,C,h,w), got {tuple(frames.shape)}")
+    B, a, b, c = frames.shape
+    B, C, h, w = (B, c, a, b) if hwc else (B, a, b, c)
+    if bgr and C < 3:
+        raise ValueError(f"{what}: bgr needs at least 3 channels, the frames have {C}")
+    return B, C, h, w
+
+
+_ORIGINS = {}     # (ys, xs, device) -> int32 (T,2) origins on the device: a handful of frame geometries per process
+
+
+def _tile_origins(ys, xs, device) -> Tensor:
+    key = (tuple(ys), tuple(xs), str(device))
+    t = _ORIGINS.get(key)
+    if t is None:
+        if len(_ORIGINS) >= 64:
+            _ORIGINS.clear()
+        t = _ORIGINS[key] = torch.tensor([(y, x) for y in ys for x in xs], dtype=torch.int32).to(device)
+    return t
+
+
+@torch.no_grad()
+def restore_frames(model, frames: Tensor, canvas: str = "square", hwc: bool = True, bgr: bool = False, tile: int = None, min_overlap: int = 128,
+                   max_batch: int = 8, out: Tensor = None) -> Tensor:
+    """``restore`` / ``restore_tiled`` for the pixels every caller starts and ends with: uint8 frames (B,h,w,C) (``hwc``, what a decoder hands over)
+    or (B,C,h,w) on the model's device in, uint8 frames of the model's ``in_chans`` channels in the same layout out (into ``out`` when given).
+    What the reference's scripts do on the host around the forward -- ``load_img``'s ``/ 255`` (utils/image_utils.py:31-35) and
+    ``img_as_ubyte(torch.clamp(restored, 0, 1))`` (test/test_gopro_hide.py:103-110) -- is one launch on each side of the model here
+    (``uf_frames_to_canvas``, ``uf_canvas_to_frames``): bit for bit the quantised ``restore(model, frames / 255, canvas=canvas)``.
+    ``bgr``: the frames are BGR(A) as cv2 decodes them; the model sees RGB(A) and the result is BGR(A) again.
+    ``tile``: frames larger than one ``tile`` x ``tile`` window (a multiple of 128) take ``restore_tiled``'s route -- the same tiles
+    (``uf_tiles_gather``), forwarded ``max_batch`` at a time into one tile-output buffer, and the same cross-fade (``uf_tiles_blend``: one launch,
+    no accumulator or weight-sum buffer); a frame that fits one tile takes the canvas route, as ``restore_tiled`` falls back to ``restore``
+    (on the square canvas)."""
+    B, C, h, w = _check_frames(frames, hwc, bgr, canvas, "restore_frames")
+    if tile is not None and tile % 128:
+        raise ValueError("restore_frames: tile must be a multiple of 128")
+    if tile is not None and (h > tile or w > tile):
+        ys, xs = _starts(h, tile, min_overlap), _starts(w, tile, min_overlap)
+        origins = _tile_origins(ys, xs, frames.device)
+        T, per = len(ys) * len(xs), max(1, max_batch // B)
+        buf = None                                                   # (T*B, in_chans, tile, tile): sized by the first output
+        for j0 in range(0, T, per):
+            j1 = min(T, j0 + per)
+            y = model(ops.tiles_gather(frames, origins[j0:j1], tile, hwc, bgr))
+            if buf is None:
+                buf = torch.empty((T * B,) + tuple(y.shape[1:]), dtype=torch.float32, device=frames.device)
+            buf[j0 * B:j1 * B].copy_(y)
+        if bgr and buf.shape[1] < 3:
+            raise ValueError(f"restore_frames: bgr needs at least 3 output channels, the model gives {buf.shape[1]}")
+        return ops.tiles_blend(buf, ys, xs, h, w, u8=True, hwc=hwc, swap_rb=bgr, out=out)
+    if canvas == "square" or tile is not None:
+        Xh = Xw = int(math.ceil(max(h, w) / 128.0) * 128)
+    else:
+        Xh, Xw = int(math.ceil(h / 128.0) * 128), int(math.ceil(w / 128.0) * 128)
+    padded, _ = ops.frames_to_canvas(frames, Xh, Xw, hwc, bgr, with_mask=False)
+    y = model(padded)
+    if bgr and y.shape[1] < 3:
+        raise ValueError(f"restore_frames: bgr needs at least 3 output channels, the model gives {y.shape[1]}")
+    return ops.canvas_to_frames(y, h, w, hwc, bgr, out=out)
+
+
+class FrameRestorer:
+    """Host uint8 frames in, host uint8 frames out, with the copies overlapped with the forward: ``depth`` (1 ... 4) slots, each with a pinned
+    input buffer, a pinned output buffer, device uint8 buffers and a stream of its own, all allocated once (at the first ``submit``).  ``submit(frames)`` copies the
+    frames (a numpy array or a CPU tensor, ``(batch,) + frame_shape``, or ``frame_shape`` alone at batch 1) into the slot's pinned buffer and
+    enqueues, on the slot's stream, the asynchronous copy to the device, ``restore_frames`` and the asynchronous copy back; it returns a
+    ticket.  ``ticket.result()`` waits for that slot and returns the restored frames in the type and rank that were submitted -- a copy, or
+    with ``copy=False`` a view of the pinned buffer that stays valid until the slot is used again.  A slot is reused only after its ticket has
+    been consumed (``submit`` raises ``RuntimeError`` otherwise); ``map`` keeps ``depth`` frames in flight and yields results in order.
+    Results are ``restore_frames``' bit for bit.  Parameters must not change while frames are in flight (``PipelinedForward``'s rule: the
+    operand pack is built on the caller's stream, which the slot stream waits for): ``drain()`` first.  No HIP graph is used."""
+
+    MAX_DEPTH = 4      # Uformer keeps 8 workspaces by stream; the library's side streams share the hardware queues with these
+
+    class Ticket:
+        def __init__(self, owner, slot, as_numpy, squeeze):
+            self._owner, self._slot, self._as_numpy, self._squeeze = owner, slot, as_numpy, squeeze
+            self._done = False
+
+        def result(self, copy: bool = True):
+            if self._done:
+                raise RuntimeError("FrameRestorer: this ticket was consumed already")
+            s = self._owner._slots[self._slot]
+            s["event"].synchronize()
+            self._done = True
+            s["ticket"] = None
+            t = s["pin_out"][0] if self._squeeze else s["pin_out"]
+            if self._as_numpy:
+                a = t.numpy()
+                return a.copy() if copy else a
+            return t.clone() if copy else t
+
+    def __init__(self, model, frame_shape, batch: int = 1, depth: int = 2, canvas: str = "rect", hwc: bool = True, bgr: bool = False, tile: int = None,
+                 min_overlap: int = 128, max_batch: int = 8, device=None):
+        if not 1 <= int(depth) <= self.MAX_DEPTH:
+            raise ValueError(f"FrameRestorer: depth must be 1 ... {self.MAX_DEPTH}, got {depth}")
+        if canvas not in ("square", "rect"):
+            raise ValueError(f"FrameRestorer: canvas must be 'square' or 'rect', got {canvas!r}")
+        frame_shape = tuple(int(v) for v in frame_shape)
+        if len(frame_shape) != 3 or min(frame_shape) < 1 or batch < 1:
+            raise ValueError(f"FrameRestorer: frame_shape must be (h,w,C) or (C,h,w) and batch positive, got {frame_shape}, batch {batch}")
+        C = frame_shape[2] if hwc else frame_shape[0]
+        if bgr and C < 3:
+            raise ValueError(f"FrameRestorer: bgr needs at least 3 channels, the frames have {C}")
+        if tile is not None and tile % 128:
+            raise ValueError("FrameRestorer: tile must be a multiple of 128")
+        out_C = int(getattr(model, "in_chans", C))
+        if bgr and out_C < 3:
+            raise ValueError(f"FrameRestorer: bgr needs at least 3 output channels, the model gives {out_C}")
+        self.model, self.batch, self.depth, self.frame_shape = model, int(batch), int(depth), frame_shape
+        self._kw = dict(canvas=canvas, hwc=hwc, bgr=bgr, tile=tile, min_overlap=min_overlap, max_batch=max_batch)
+        self._in_shape = (self.batch,) + frame_shape
+        self._out_shape = (self.batch,) + (frame_shape[:2] + (out_C,) if hwc else (out_C,) + frame_shape[1:])
+        self._device, self.device = device, None
+        self._slots, self._closed, self._k = None, False, 0
+
+    def _allocate(self) -> None:
+        """the slots, once, at the first submit (so that the argument checks of the constructor and of submit need no device)"""
+        dev = torch.device(self._device) if self._device is not None else next(self.model.parameters()).device
+        if dev.type != "cuda":
+            raise ops.UformerHipError(f"FrameRestorer runs on the GPU only (the model is on {dev}); there is no CPU path")
+        self.device = dev
+        self._slots = [dict(pin_in=torch.empty(self._in_shape, dtype=torch.uint8).pin_memory(), pin_out=torch.empty(self._out_shape, dtype=torch.uint8).pin_memory(),
+                            dev_in=torch.empty(self._in_shape, dtype=torch.uint8, device=dev), dev_out=torch.empty(self._out_shape, dtype=torch.uint8, device=dev),
+                            stream=torch.cuda.Stream(device=dev), event=torch.cuda.Event(), ticket=None, pack=None) for _ in range(self.depth)]
+
+    @torch.no_grad()
+    def submit(self, frames) -> "FrameRestorer.Ticket":
+        if self._closed:
+            raise RuntimeError("FrameRestorer: closed")
+        as_numpy = not isinstance(frames, torch.Tensor)
+        t = torch.from_numpy(frames) if as_numpy else frames
+        if t.dtype != torch.uint8:
+            raise ValueError(f"FrameRestorer: frames must be uint8, got {t.dtype}")
+        squeeze = self.batch == 1 and tuple(t.shape) == self.frame_shape
+        if not squeeze and tuple(t.shape) != self._in_shape:
+            raise ValueError(f"FrameRestorer: frames must be {self._in_shape}, got {tuple(t.shape)}")
+        if t.is_cuda:
+            raise ValueError("FrameRestorer takes host frames; restore_frames takes frames on the device")
+        if self._slots is None:
+            self._allocate()
+        s = self._slots[self._k % self.depth]
+        if s["ticket"] is not None:
+            raise RuntimeError("FrameRestorer: the slot's previous result was not consumed; call result() on its ticket first")
+        self._k += 1
+        (s["pin_in"][0] if squeeze else s["pin_in"]).copy_(t)
+        # the operand pack is (re)built on the caller's stream, which the slot stream waits for, as PipelinedForward.submit does; the slot keeps the pack
+        # it ran on alive until it is used again
+        get = getattr(self.model, "_get_packed", None)
+        s["pack"] = get(self.device) if get is not None else None
+        st = s["stream"]
+        st.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(st):
+            s["dev_in"].copy_(s["pin_in"], non_blocking=True)
+            restore_frames(self.model, s["dev_in"], out=s["dev_out"], **self._kw)
+            s["pin_out"].copy_(s["dev_out"], non_blocking=True)
+            s["event"].record(st)
+        s["ticket"] = FrameRestorer.Ticket(self, (self._k - 1) % self.depth, as_numpy, squeeze)
+        return s["ticket"]
+
+    def map(self, iterable):
+        """Generator: the restored frames of an iterable of frames, ``depth`` in flight, in order (copies)."""
+        pending = []
+        for frames in iterable:
+            if len(pending) >= self.depth:
+                yield pending.pop(0).result()
+            pending.append(self.submit(frames))
+        while pending:
+            yield pending.pop(0).result()
+
+    def drain(self) -> None:
+        """wait on the host for everything submitted so far (before a parameter update, a checkpoint load, ...); tickets stay valid"""
+        for s in self._slots or ():
+            s["stream"].synchronize()
+
+    def close(self) -> None:
+        """drain and release the buffers; outstanding ``copy=False`` views and tickets become invalid"""
+        self.drain()
+        self._slots, self._closed = None, True

@@ -822,6 +822,85 @@ def crop_augment(frames: Tensor, meta: Tensor, ps: int, hwc: bool = False) -> Te
     return out
 
 
+def _frame_dims(frames: Tensor, hwc: bool, what: str):
+    if frames.dim() != 4:
+        raise UformerHipError(f"{what}: frames must be (B,h,w,C) or (B,C,h,w), got {tuple(frames.shape)}")
+    B, a, b, c = frames.shape
+    return (B, c, a, b) if hwc else (B, a, b, c)                # B, C, h, w
+
+
+def _u8_frames(B: int, Cc: int, h: int, w: int, hwc: bool, device, out: Optional[Tensor], what: str) -> Tensor:
+    shape = (B, h, w, Cc) if hwc else (B, Cc, h, w)
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != device:
+        raise UformerHipError(f"{what}: out must be a contiguous uint8 tensor of shape {shape} on {device}")
+    return out
+
+
+def frames_to_canvas(frames: Tensor, Xh: int, Xw: int, hwc: bool = True, swap_rb: bool = False, with_mask: bool = False):
+    """uint8 frames (B,h,w,C) (``hwc``) or (B,C,h,w) -> f32 canvas (B,C,Xh,Xw) = u / 255 at ((Xh-h)//2, (Xw-w)//2), zero elsewhere, + the
+    (B,1,Xh,Xw) mask (or None): ``expand_canvas`` of the float frames bit for bit, one launch.  ``swap_rb``: BGR(A) frames to RGB(A) planes."""
+    _dev(frames)
+    if frames.dtype != torch.uint8:
+        raise UformerHipError("frames_to_canvas: frames must be uint8")
+    B, Cc, h, w = _frame_dims(frames, hwc, "frames_to_canvas")
+    canvas = torch.empty((B, Cc, Xh, Xw), dtype=torch.float32, device=frames.device)
+    mask = torch.empty((B, 1, Xh, Xw), dtype=torch.float32, device=frames.device) if with_mask else None
+    _launch("uf_frames_to_canvas", frames.device, _c(frames), int(hwc), int(swap_rb), canvas, mask, B, Cc, h, w, Xh, Xw)
+    return canvas, mask
+
+
+def canvas_to_frames(canvas: Tensor, h: int, w: int, hwc: bool = True, swap_rb: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """Inverse of frames_to_canvas: crop + clamp to [0,1] + quantise, ``img_as_ubyte(clamp(x, 0, 1))`` for float32 (rint of the f32 product
+    with 255, ties to even; NaN gives 0), as uint8 (B,h,w,C) or (B,C,h,w); ``out`` receives the frames when given."""
+    _dev(canvas)
+    B, Cc, Xh, Xw = canvas.shape
+    frames = _u8_frames(B, Cc, h, w, hwc, canvas.device, out, "canvas_to_frames")
+    _launch("uf_canvas_to_frames", canvas.device, _c(canvas, torch.float32), frames, int(hwc), int(swap_rb), B, Cc, h, w, Xh, Xw)
+    return frames
+
+
+def tiles_gather(frames: Tensor, origins: Tensor, tile: int, hwc: bool = False, swap_rb: bool = False) -> Tensor:
+    """The tile batch of ``infer.restore_tiled``: frames uint8 (divided by 255) or f32, (B,h,w,C) (``hwc``) or (B,C,h,w); origins int32 (T,2) =
+    (y, x) on the device -> f32 (T*B, C, tile, tile), entry k*B + b = frame b from origin k, zero beyond the frame."""
+    _dev(frames, origins)
+    if frames.dtype not in (torch.uint8, torch.float32):
+        raise UformerHipError("tiles_gather: frames must be uint8 or float32")
+    B, Cc, h, w = _frame_dims(frames, hwc, "tiles_gather")
+    if origins.dim() != 2 or origins.shape[1] != 2:
+        raise UformerHipError(f"tiles_gather: origins must be (T,2), got {tuple(origins.shape)}")
+    T = origins.shape[0]
+    tiles = torch.empty((T * B, Cc, tile, tile), dtype=torch.float32, device=frames.device)
+    _launch("uf_tiles_gather", frames.device, _c(frames), int(frames.dtype == torch.uint8), int(hwc), int(swap_rb), tiles, _c(origins, torch.int32),
+            T, B, Cc, h, w, tile)
+    return tiles
+
+
+def tiles_blend(tiles_out: Tensor, ys, xs, h: int, w: int, u8: bool = False, hwc: bool = True, swap_rb: bool = False, clamp: bool = True,
+                out: Optional[Tensor] = None) -> Tensor:
+    """Cross-fade of restored tiles (len(ys)*len(xs)*B, C, tile, tile), job order [(y,x) for y in ys for x in xs], into frames of (h, w):
+    sum of ramp weight x tile over the sum of the weights (``infer.restore_tiled``'s blend, one launch, no accumulator).  f32 planes
+    (B,C,h,w), clamped to [0,1] with ``clamp``; ``u8``: uint8 frames (B,h,w,C) (``hwc``) or (B,C,h,w) through canvas_to_frames' quantiser."""
+    _dev(tiles_out)
+    ys, xs = [int(v) for v in ys], [int(v) for v in xs]
+    n, Cc, tile, tile2 = tiles_out.shape
+    if tile != tile2 or not ys or not xs or n % (len(ys) * len(xs)):
+        raise UformerHipError(f"tiles_blend: {tuple(tiles_out.shape)} is no batch of square tiles for {len(ys)} x {len(xs)} origins")
+    B = n // (len(ys) * len(xs))
+    if u8:
+        res = _u8_frames(B, Cc, h, w, hwc, tiles_out.device, out, "tiles_blend")
+    elif out is None:
+        res = torch.empty((B, Cc, h, w), dtype=torch.float32, device=tiles_out.device)
+    else:
+        if out.dtype != torch.float32 or tuple(out.shape) != (B, Cc, h, w) or not out.is_contiguous() or out.device != tiles_out.device:
+            raise UformerHipError(f"tiles_blend: out must be a contiguous float32 tensor of shape {(B, Cc, h, w)} on {tiles_out.device}")
+        res = out
+    _launch("uf_tiles_blend", tiles_out.device, _c(tiles_out, torch.float32), (ctypes.c_int * len(ys))(*ys), len(ys), (ctypes.c_int * len(xs))(*xs), len(xs),
+            res, int(u8), int(hwc), int(swap_rb), int(clamp), B, Cc, h, w, tile)
+    return res
+
+
 def mixup(x: Tensor, lam: Tensor, perm: Tensor) -> Tensor:
     """lam[b] x[b] + (1 - lam[b]) x[perm[b]] (utils/dataset_utils.py:44-53)."""
     _dev(x, lam, perm)
