@@ -56,7 +56,9 @@ int uf_timing_enable(int on);
 int uf_timing_report(char* json, size_t n);
 /* development aid: device buffer of u64 that instrumented kernels fill -- sampled phase stamps in entries [0, 65536),
  * then one 8-entry census record per workgroup {s_memtime start, end, 100 MHz clock start, end, HW_ID|XCC_ID<<32}: the
- * buffer must hold 65536 + 8 * (largest grid) entries.  NULL = off (the default). */
+ * buffer must hold 65536 + 8 * (largest grid) entries.  NULL = off (the default).
+ * Only the diagnostic build (-DUF_STAMPS=1, scripts/build_variant.sh --stamps) has instrumented kernels.  The shipped library
+ * carries no stamps: it returns UF_ERR_UNSUPPORTED for a non-NULL buffer, never writes to it, and returns UF_OK for NULL. */
 int uf_debug_set_tbuf(void* p);
 
 /* ---- fragment-major weights ------------------------------------------------------------------

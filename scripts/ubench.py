@@ -1,5 +1,13 @@
 #!/usr/bin/env python3
-"""Micro-benchmark single C-ABI entry points on the Uformer-B stage shapes (MI355X)."""
+"""Micro-benchmark single C-ABI entry points on the Uformer-B stage shapes (MI355X).
+
+The timing commands (lngemm, blocks) run on the shipped library.  The stamp and census commands (stamps, stamps2, stamps3, census, census2)
+read in-kernel cycle stamps, which the shipped kernels do not carry: they need the diagnostic build,
+
+    scripts/build_variant.sh --stamps
+    UFORMER_HIP_LIB=ab/stamps/libuformer_hip.so python scripts/ubench.py stamps
+
+and stop with a message when the loaded library refuses the stamp buffer.  Read a stamped build's SHARES, never its run time."""
 import os
 import sys
 import time
@@ -8,10 +16,20 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 # uf_debug_set_tbuf buffer: sampled phase stamps in the first 65536 entries, then the per-workgroup census
-# (8 entries per workgroup, uf_common.h struct Census) for up to 32768 workgroups
+# (8 entries per workgroup, uf_stamps.h struct Census) for up to 32768 workgroups
 TBUF_ELEMS = 65536 + 8 * 32768
 
 from uformer_amd import ops
+
+
+def set_tbuf(lib, tb):
+    """hand the stamp buffer to the library; a library built without kernel stamps (the shipped one) refuses it"""
+    from uformer_amd import _lib
+    rc = lib.uf_debug_set_tbuf(tb.data_ptr())
+    if rc != 0:
+        sys.exit(f"ubench: {_lib.LIB_PATH} refused the stamp buffer (rc {rc}: {_lib.last_error()}).\n"
+                 "This command needs the diagnostic build: scripts/build_variant.sh --stamps, then "
+                 "UFORMER_HIP_LIB=ab/stamps/libuformer_hip.so python scripts/ubench.py " + " ".join(sys.argv[1:]))
 
 
 def timeit(fn, n=20, warm=3):
@@ -88,7 +106,7 @@ def bench_stamps():
         for _ in range(3):
             lib.uf_lewin_block_fwd(bp, x.data_ptr(), C, B, H, H, C, None, 0, 1, ws.data_ptr(), nbytes, st)
         torch.cuda.synchronize()
-        lib.uf_debug_set_tbuf(tb.data_ptr())
+        set_tbuf(lib, tb)
         lib.uf_lewin_block_fwd(bp, x.data_ptr(), C, B, H, H, C, None, 0, 1, ws.data_ptr(), nbytes, st)
         torch.cuda.synchronize()
         lib.uf_debug_set_tbuf(None)
@@ -121,7 +139,7 @@ def bench_stamps_leff2():
         for _ in range(3):
             lib.uf_leff_fwd(bp, x.data_ptr(), C, B, H, H, C, 1, ws.data_ptr(), nbytes, st)
         torch.cuda.synchronize()
-        lib.uf_debug_set_tbuf(tb.data_ptr())
+        set_tbuf(lib, tb)
         lib.uf_leff_fwd(bp, x.data_ptr(), C, B, H, H, C, 1, ws.data_ptr(), nbytes, st)
         torch.cuda.synchronize()
         lib.uf_debug_set_tbuf(None)
@@ -151,7 +169,7 @@ def bench_stamps_lngemm():
             ops.ln_linear_gelu(x, g, b, w1, b1)
         tb = torch.zeros(TBUF_ELEMS, dtype=torch.int64, device="cuda")
         torch.cuda.synchronize()
-        lib.uf_debug_set_tbuf(tb.data_ptr())
+        set_tbuf(lib, tb)
         ops.ln_linear_gelu(x, g, b, w1, b1)
         torch.cuda.synchronize()
         lib.uf_debug_set_tbuf(None)
@@ -211,7 +229,7 @@ def bench_census():
         for _ in range(2):
             h1 = ops.ln_linear_gelu(x, g, b, w1, b1)
         torch.cuda.synchronize()
-        lib.uf_debug_set_tbuf(tb.data_ptr())
+        set_tbuf(lib, tb)
         h1 = ops.ln_linear_gelu(x, g, b, w1, b1)
         torch.cuda.synchronize()
         lib.uf_debug_set_tbuf(None)
@@ -221,7 +239,7 @@ def bench_census():
             ops.dwconv_linear2(h1.reshape(B, H, H, 4 * C), wd, bd, w2, b2, xr)
         tb.zero_()
         torch.cuda.synchronize()
-        lib.uf_debug_set_tbuf(tb.data_ptr())
+        set_tbuf(lib, tb)
         ops.dwconv_linear2(h1.reshape(B, H, H, 4 * C), wd, bd, w2, b2, xr)
         torch.cuda.synchronize()
         lib.uf_debug_set_tbuf(None)
@@ -250,7 +268,7 @@ def bench_census_attn():
             lib.uf_lewin_attn_fwd(bp, x.data_ptr(), C, B, H, H, C, None, 0, 1, ws.data_ptr(), nbytes, st)
         t_us = timeit(lambda: lib.uf_lewin_attn_fwd(bp, x.data_ptr(), C, B, H, H, C, None, 0, 1, ws.data_ptr(), nbytes, st), n=10, warm=1)
         torch.cuda.synchronize()
-        lib.uf_debug_set_tbuf(tb.data_ptr())
+        set_tbuf(lib, tb)
         lib.uf_lewin_attn_fwd(bp, x.data_ptr(), C, B, H, H, C, None, 0, 1, ws.data_ptr(), nbytes, st)
         torch.cuda.synchronize()
         lib.uf_debug_set_tbuf(None)

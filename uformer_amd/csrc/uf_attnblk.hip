@@ -47,7 +47,7 @@ struct AttnBlkParams {
     int n_windows, H, W, shift;
     float qscale;
     float qscale_plain;                    // head_dim^-0.5 without the log2(e) of the softmax domain: the q the backward reads
-    unsigned long long* tbuf;   // optional phase timestamps (uf_debug_set_tbuf)
+    unsigned long long* tbuf;   // diagnostic build (UF_STAMPS): phase timestamps (uf_debug_set_tbuf); never read otherwise
 };
 
 constexpr float LOG2E = 1.4426950408889634f;
@@ -232,8 +232,10 @@ __global__ __launch_bounds__(NT, (attn_waves_per_simd<T, C, NT, LR>())) void att
     const int fr = lane & 15, fg = lane >> 4;
     const int bw = blockIdx.x;                      // window index (image-major, as window_partition)
     const WinGeom geo = window_geom(bw, p.H, p.W, p.shift);      // window coordinates once (scalar unit), rows by adds
-    auto stamp = [&](int k) {
-        if (p.tbuf && lane == 0 && (bw & 63) == 0) p.tbuf[((bw >> 6) * WAVES + wave) * 16 + k] = __builtin_readcyclecounter();
+    auto stamp = [&]([[maybe_unused]] int k) {      // phase timestamps of sampled windows: diagnostic build only (UF_STAMPS), nothing otherwise
+        if constexpr (UF_STAMPS != 0) {
+            if (p.tbuf && lane == 0 && (bw & 63) == 0) p.tbuf[((bw >> 6) * WAVES + wave) * 16 + k] = stamp_now();
+        }
     };
     stamp(0);
     Census census; census.begin();

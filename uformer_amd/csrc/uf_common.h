@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "../../include/uformer_hip.h"
+#include "uf_stamps.h"   // UF_STAMPS, Census, LapTimer, stamp_now: in-kernel instrumentation, empty in the shipped build
 
 namespace uf {
 
@@ -157,22 +158,6 @@ template <typename T> struct Chunk<T, 4> {
     static __device__ __forceinline__ Raw pack(const float* f) {
         if constexpr (sizeof(T) == 2) return Raw{pack2<T>(f[0], f[1]), pack2<T>(f[2], f[3])};
         else return Raw{__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), __float_as_uint(f[3])};
-    }
-};
-
-// ------------------------------------------------------------------------------------
-// debug census (uf_debug_set_tbuf): every workgroup records where and when it ran, so the host can count how many
-// workgroups a CU really held at once and the effective shader clock.  Entry b at tbuf[65536 + 8 b]:
-// {s_memtime start, end, wall_clock64 (100 MHz) start, end, HW_ID | XCC_ID << 32}.
-// ------------------------------------------------------------------------------------
-struct Census {
-    unsigned long long t0, r0;
-    __device__ __forceinline__ void begin() { t0 = __builtin_readcyclecounter(); r0 = wall_clock64(); }
-    __device__ __forceinline__ void end(unsigned long long* tbuf, unsigned block) const {
-        if (!tbuf || threadIdx.x != 0) return;
-        unsigned long long* o = tbuf + 65536 + (size_t)block * 8;
-        o[0] = t0; o[1] = __builtin_readcyclecounter(); o[2] = r0; o[3] = wall_clock64();
-        o[4] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
     }
 };
 

@@ -176,8 +176,18 @@ extern "C" int uf_timing_report(char* json, size_t n) {
 }
 
 namespace uf { void debug_set_tbuf(void* p); }
-// development aid: device buffer that instrumented kernels fill with s_memtime stamps (NULL = off)
-extern "C" int uf_debug_set_tbuf(void* p) { uf::debug_set_tbuf(p); return UF_OK; }
+// development aid: device buffer that the kernels of the diagnostic build (UF_STAMPS=1, uf_stamps.h) fill with cycle stamps (NULL = off).
+// The shipped kernels carry no stamps: this build refuses a buffer instead of leaving it silently unwritten.
+extern "C" int uf_debug_set_tbuf(void* p) {
+#if !UF_STAMPS
+    if (p) {
+        uf::set_error("uf_debug_set_tbuf: this library is built without kernel stamps; use the diagnostic build (-DUF_STAMPS=1, scripts/build_variant.sh --stamps) through UFORMER_HIP_LIB");
+        return UF_ERR_UNSUPPORTED;
+    }
+#endif
+    uf::debug_set_tbuf(p);
+    return UF_OK;
+}
 
 extern "C" int uf_version(void) { return UF_ABI_VERSION; }
 

@@ -27,7 +27,7 @@ struct Leff2Params {
     const float* drop;              // training: per-image DropPath scale of the branch (model.py:987) or NULL
     int B, H, W;
     int n_tiles;                // B * (H / 8) * (W / 8): a workgroup walks tiles blockIdx.x, blockIdx.x + gridDim.x, ... (persistent launch: gridDim.x < n_tiles)
-    unsigned long long* tbuf;   // optional per-role cycle totals of sampled blocks (uf_debug_set_tbuf)
+    unsigned long long* tbuf;   // diagnostic build (UF_STAMPS): per-role cycle totals of sampled blocks (uf_debug_set_tbuf); never read otherwise
 };
 
 constexpr int KCW = 64;  // hidden channels one producer group (4 waves) convolves per interval
@@ -119,7 +119,7 @@ __global__ __launch_bounds__((PW * NPG + NC) * 64, WPS) void leff2_kernel(const 
     const int G = (int)gridDim.x;
     const int nk = (p.n_tiles - (int)blockIdx.x + G - 1) / G;
     const int NTOT = nk * NIT;
-    const int bt = xcd_tile(blockIdx.x, p.n_tiles);               // first tile: census / stamp index
+    [[maybe_unused]] const int bt = xcd_tile(blockIdx.x, p.n_tiles);   // first tile: census / stamp index (diagnostic build)
     auto tile_coords = [&](int k, int& b, int& y0, int& x0) {
         const int t = xcd_tile((int)blockIdx.x + k * G, p.n_tiles);
         b = t / (tiles_x * tiles_y);
@@ -207,7 +207,7 @@ __global__ __launch_bounds__((PW * NPG + NC) * 64, WPS) void leff2_kernel(const 
             if (it < NTOT) issue(it);
         wait_dma<0>();
         lds_barrier();                                                          // B0: intervals 0 .. NBUF-2 staged
-        unsigned long long tw = 0, tbar = 0, t0 = __builtin_readcyclecounter(), t1;
+        LapTimer<2> role; role.start();                                         // diagnostic build: cycles at work / at the barrier
 #pragma unroll 1
         for (int i = 0; i <= NTOT; ++i) {                       // i = flattened interval
             if (i + NBUF - 1 < NTOT) issue(i + NBUF - 1);       // ring slot last read in iteration i-1
@@ -251,13 +251,15 @@ __global__ __launch_bounds__((PW * NPG + NC) * 64, WPS) void leff2_kernel(const 
                 }
                 }
             }
-            t1 = __builtin_readcyclecounter(); tw += t1 - t0; t0 = t1;
+            role.lap(0);
             // interval i+1 must have landed before anyone passes the barrier; later intervals stay in flight
             if (NBUF >= 3 && i + NBUF - 1 < NTOT) wait_dma<(NBUF - 2) * NS>(); else wait_dma<0>();
             lds_barrier();
-            t1 = __builtin_readcyclecounter(); tbar += t1 - t0; t0 = t1;
+            role.lap(1);
         }
-        if (p.tbuf && lane == 0 && (bt & 63) == 0) { p.tbuf[((bt >> 6) * 16 + wave) * 4] = tw; p.tbuf[((bt >> 6) * 16 + wave) * 4 + 1] = tbar; p.tbuf[((bt >> 6) * 16 + wave) * 4 + 2] = producer; }
+        if constexpr (UF_STAMPS != 0) {
+            if (p.tbuf && lane == 0 && (bt & 63) == 0) { p.tbuf[((bt >> 6) * 16 + wave) * 4] = role.total(0); p.tbuf[((bt >> 6) * 16 + wave) * 4 + 1] = role.total(1); p.tbuf[((bt >> 6) * 16 + wave) * 4 + 2] = producer; }
+        }
         return;
     }
 
@@ -299,17 +301,40 @@ __global__ __launch_bounds__((PW * NPG + NC) * 64, WPS) void leff2_kernel(const 
     // the W2 fragments of the next sub-chunk are requested as soon as the registers are free -- across the barrier between
     // intervals, so their L2 round trip hides under the wait for the stencil.  After the last interval of a tile: epilogue
     // (+ bias + residual, in place on the f32 stream, model.py:987), accumulators back to zero.  Where the registers allow
-    // (C <= 128) the residual rows of a tile are requested at the start of its last interval.
+    // (C <= 64) the residual rows of a tile are requested at the start of its last interval.
     constexpr bool XPRE = SZ == 2 && TNW * TMW <= 4 && CP == 0;        // C <= 64 (16 registers); at C = 128 the 32 registers spill under the 80-register bound
     f32x4 xres[XPRE ? TNW : 1][XPRE ? TMW : 1];
+    // Residual rows in GROUPS (XGRP): the epilogue requests XG row tiles, then adds and stores them -- one HBM round trip per group.  Row by row
+    // (load -> wait -> add -> store -> next load) every row tile is a round trip of its own, because the compiler may not move a load of p.x
+    // above the store before it: 7 dependent trips per tile and wave at C = 128, 14 at C >= 256, with the next tile's first barrier waiting
+    // behind them.  Hoisting a group's loads above the stores before them is safe: a wave's 16 x 16 tiles never overlap each other or another
+    // wave's, and a tile's rows are written by this one workgroup.  Each element is still r + (acc + b2) * dscale, evaluated as before.
+    // A group = the TMW row tiles of one column tile i at C = 128 (16 registers, free once the operand fragments of the last k-step are dead);
+    // pairs at C = 256 on 4 consumers, whose 64 accumulator registers sit under a 128-register bound.  Only these instances use groups: the ones
+    // whose own symbol measured faster with them in the one-stream kernel trace (profiles/stamps_epilogue.json).  C = 256 on 8
+    // consumers and C = 512 were not faster with groups (with or without the first group requested an interval ahead) and keep the row-by-row
+    // loop, as do the C = 512 form that "leff2=1" forces (no model run reaches it: not measured) and the f32 forms (parity mode, not measured).
+    constexpr bool XGRP = SZ == 2 && CP == 0 && (C == 128 || (C == 256 && NC == 4));
+    constexpr int XG = !XGRP ? 1 : (C == 128 ? TMW : 2);
+    static_assert(TMW % XG == 0, "residual groups");
+    // Address of a row tile.  Grouped form: wave-uniform row base (image, tile, row pair 2 (wm TMW + j)) + this lane's place inside a row pair,
+    // with the base pinned in scalar registers -- otherwise the compiler hoists one 64-bit per-lane address per row tile out of the interval
+    // loop, and those spill under the register bounds of C >= 128 once a group's rows are in flight together.
+    [[maybe_unused]] const size_t xlane = ((size_t)(fr >> 3) * p.W + (fr & 7)) * p.ld + wn * TNW * 16 + fg * 4;
     auto x_ptr = [&](int b, int y0, int x0, int i, int j) -> float* {
-        const int n = (wn * TNW + i) * 16 + fg * 4;
-        const int pm = (wm * TMW + j) * 16 + fr;
-        return p.x + ((size_t)(b * p.H + y0 + (pm >> 3)) * p.W + x0 + (pm & 7)) * p.ld + n;
+        if constexpr (!XGRP) {
+            const int n = (wn * TNW + i) * 16 + fg * 4;
+            const int pm = (wm * TMW + j) * 16 + fr;
+            return p.x + ((size_t)(b * p.H + y0 + (pm >> 3)) * p.W + x0 + (pm & 7)) * p.ld + n;
+        } else {
+            size_t row = ((size_t)(b * p.H + y0 + 2 * (wm * TMW + j)) * p.W + x0) * p.ld;
+            asm volatile("" : "+s"(row));       // the offset, not the pointer: p.x stays a global-memory address for the compiler
+            return p.x + row + xlane + i * 16;
+        }
     };
     w2_issue(0);
     lds_barrier();                                         // B0
-    unsigned long long ctw = 0, ctbar = 0, ct0 = __builtin_readcyclecounter(), ct1;
+    LapTimer<2> role; role.start();
 #pragma unroll 1
     for (int j = 0; j <= NTOT; ++j) {
         if (j >= 1) {
@@ -351,13 +376,28 @@ __global__ __launch_bounds__((PW * NPG + NC) * 64, WPS) void leff2_kernel(const 
 #pragma unroll
                 for (int i = 0; i < TNW; ++i) {
                     const f32x4 b2 = *reinterpret_cast<const f32x4*>(p.b2 + (wn * TNW + i) * 16 + fg * 4);
+                    if constexpr (XGRP) {
 #pragma unroll
-                    for (int jj = 0; jj < TMW; ++jj) {
-                        float* xp = x_ptr(tb, ty0, tx0, i, jj);
-                        f32x4 r;
-                        if constexpr (XPRE) r = xres[i][jj]; else r = *reinterpret_cast<const f32x4*>(xp);
-                        *reinterpret_cast<f32x4*>(xp) = r + (acc[i][jj] + b2) * dscale;
-                        acc[i][jj] = f32x4{0.f, 0.f, 0.f, 0.f};
+                        for (int j0 = 0; j0 < TMW; j0 += XG) {
+                            f32x4 r[XG];
+#pragma unroll
+                            for (int q = 0; q < XG; ++q) r[q] = *reinterpret_cast<const f32x4*>(x_ptr(tb, ty0, tx0, i, j0 + q));      // the group's rows first ...
+                            __builtin_amdgcn_sched_barrier(0);      // ... with acc + b2 behind them: else the bias is waited for (vmcnt(0)) before the rows are requested
+#pragma unroll
+                            for (int q = 0; q < XG; ++q) {                                                                          // ... then its adds and stores
+                                *reinterpret_cast<f32x4*>(x_ptr(tb, ty0, tx0, i, j0 + q)) = r[q] + (acc[i][j0 + q] + b2) * dscale;
+                                acc[i][j0 + q] = f32x4{0.f, 0.f, 0.f, 0.f};
+                            }
+                        }
+                    } else {
+#pragma unroll
+                        for (int jj = 0; jj < TMW; ++jj) {
+                            float* xp = x_ptr(tb, ty0, tx0, i, jj);
+                            f32x4 r;
+                            if constexpr (XPRE) r = xres[i][jj]; else r = *reinterpret_cast<const f32x4*>(xp);
+                            *reinterpret_cast<f32x4*>(xp) = r + (acc[i][jj] + b2) * dscale;
+                            acc[i][jj] = f32x4{0.f, 0.f, 0.f, 0.f};
+                        }
                     }
                 }
             }
@@ -369,16 +409,14 @@ __global__ __launch_bounds__((PW * NPG + NC) * 64, WPS) void leff2_kernel(const 
                 mconv_job<T, 1, KC, SAT, 2 * HW_ * PS>(Hs, Wl, At0 + (j & 1) * AT_BYTES, gq, 4 - CP + (cw >> 2), boff, msk, hshift, fr, fg);
             }
         }
-        ct1 = __builtin_readcyclecounter(); ctw += ct1 - ct0; ct0 = ct1;
+        role.lap(0);
         lds_barrier();
-        ct1 = __builtin_readcyclecounter(); ctbar += ct1 - ct0; ct0 = ct1;
+        role.lap(1);
     }
-    if (p.tbuf && lane == 0 && (bt & 63) == 0) { p.tbuf[((bt >> 6) * 16 + wave) * 4] = ctw; p.tbuf[((bt >> 6) * 16 + wave) * 4 + 1] = ctbar; p.tbuf[((bt >> 6) * 16 + wave) * 4 + 2] = 0; }
-    if (cw == 0 && lane == 0) {   // census entry written by the first consumer thread (thread 0 is a producer and has returned)
-        Census c2 = census;
-        if (p.tbuf) { unsigned long long* o = p.tbuf + 65536 + (size_t)bt * 8; o[0] = c2.t0; o[1] = __builtin_readcyclecounter(); o[2] = c2.r0; o[3] = wall_clock64();
-            o[4] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32); }
+    if constexpr (UF_STAMPS != 0) {
+        if (p.tbuf && lane == 0 && (bt & 63) == 0) { p.tbuf[((bt >> 6) * 16 + wave) * 4] = role.total(0); p.tbuf[((bt >> 6) * 16 + wave) * 4 + 1] = role.total(1); p.tbuf[((bt >> 6) * 16 + wave) * 4 + 2] = 0; }
     }
+    census.end(p.tbuf, bt, cw == 0 && lane == 0);   // census entry written by the first consumer thread (thread 0 is a producer and has returned)
 }
 
 template <typename T, int C, int NPG, int NC, int NBUF, int WPS, int PW = 4, int CP = 0>

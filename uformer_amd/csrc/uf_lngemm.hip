@@ -35,7 +35,7 @@ struct LnGemmParams {
     int H, W, windowed, shift;
     void* out; int ldo;              // EP_GELU: T[M][ldo]
     void* q; void* k; void* vt; int heads, hd; float qscale;  // EP_QKV
-    unsigned long long* tbuf;        // optional cycle stamps (uf_debug_set_tbuf)
+    unsigned long long* tbuf;        // diagnostic build (UF_STAMPS): cycle stamps (uf_debug_set_tbuf); never read otherwise
 };
 
 enum { EP_QKV = 0, EP_GELU = 1 };
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256, 2) void ln_gemm_kernel(const LnGemmParams p) {
     char* stg = smem + BM * SA + wave * (16 * SS);
     const int m0 = blockIdx.x * BM;
     Census census; census.begin();
-    unsigned long long ts0 = __builtin_readcyclecounter(), ts_ln = 0, ts_k = 0, ts_e = 0, tsx;
+    LapTimer<3> ts; ts.start();      // diagnostic build: cycles in the LayerNorm (0), the k-loops (1) and the epilogues (2)
 
     // ---------------- phase 0: LayerNorm (+gather, +modulator) into LDS -------------------------
     {
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256, 2) void ln_gemm_kernel(const LnGemmParams p) {
         }
     }
     lds_barrier();
-    tsx = __builtin_readcyclecounter(); ts_ln = tsx - ts0; ts0 = tsx;
+    ts.lap(0);
 
     // ---------------- phase 1: barrier-free walk over 64 x 64 output units -------------------------
     // blockIdx.y splits the 64-wide column groups when M alone gives too few blocks for 256 CUs
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(256, 2) void ln_gemm_kernel(const LnGemmParams p) {
     if (wave < n_units) unit_prefetch(wave);
 #pragma unroll 1
     for (int u = wave; u < n_units; u += 4) {
-        tsx = __builtin_readcyclecounter(); ts_e += tsx - ts0; ts0 = tsx;   // time since the previous k-loop ended = epilogue
+        ts.lap(2);   // time since the previous k-loop ended = epilogue
         const int mh = u % MH, ng = g0 + u / MH;
         const int nbase = ng * 64, mbase = mh * 64;
         // number of leading n-tiles of this unit that are NOT in the V third (wave-uniform)
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256, 2) void ln_gemm_kernel(const LnGemmParams p) {
         else kloop(std::integral_constant<int, 2>{});
         if (u + 4 < n_units) unit_prefetch(u + 4);
         __builtin_amdgcn_sched_barrier(0);
-        tsx = __builtin_readcyclecounter(); ts_k += tsx - ts0; ts0 = tsx;
+        ts.lap(1);
 
         // per-tile destination info for the q/k/v^T layouts, once per unit (scalar): tile i covers
         // channels [nbase+16i, +16) = 16 consecutive d of ONE head of q, k or v.
@@ -326,11 +326,13 @@ __global__ __launch_bounds__(256, 2) void ln_gemm_kernel(const LnGemmParams p) {
             }
         }
     }
-    tsx = __builtin_readcyclecounter(); ts_e += tsx - ts0;
+    ts.lap(2);
     census.end(p.tbuf, blockIdx.y * gridDim.x + blockIdx.x);
-    if (p.tbuf && lane == 0 && (blockIdx.x & 63) == 0 && blockIdx.y == 0) {
-        unsigned long long* o = p.tbuf + ((blockIdx.x >> 6) * 4 + wave) * 4;
-        o[0] = ts_ln; o[1] = ts_k; o[2] = ts_e; o[3] = n_units;
+    if constexpr (UF_STAMPS != 0) {
+        if (p.tbuf && lane == 0 && (blockIdx.x & 63) == 0 && blockIdx.y == 0) {
+            unsigned long long* o = p.tbuf + ((blockIdx.x >> 6) * 4 + wave) * 4;
+            o[0] = ts.total(0); o[1] = ts.total(1); o[2] = ts.total(2); o[3] = n_units;
+        }
     }
 }
 
