@@ -583,6 +583,27 @@ int uf_tiles_gather(const void* src, int src_is_u8, int src_hwc, int swap_rb, fl
                     int tile, void* stream);
 int uf_tiles_blend(const float* tiles_out, const int* ys, int ny, const int* xs, int nx, void* out, int out_is_u8, int out_hwc, int swap_rb,
                    int clamp01, int B, int C, int h, int w, int tile, void* stream);
+/* ---- geometric self-ensemble: the image under the eight flips and rotations as one batch, and the mean of the results --------
+ * T_k, k = 0 ... 7, is Augment_RGB_torch.transform<k> (utils/dataset_utils.py:8-33; uf_crop_augment's numbering): rot90 by k & 3 in dims [-1,-2],
+ * then flip(-2) for k >= 4.  Odd k turn an (h, w) image into a (w, h) member.  T_1 and T_3 are each other's inverse, every other T_k is its own.
+ * A member list ks is an int32 array ON THE HOST (it travels as a kernel argument): distinct, ascending, all of one parity.
+ *
+ * uf_tta_gather: src as uf_tiles_gather takes it (u8 divided by 255, or f32; (B,h,w,C) or (B,C,h,w); C = 1 ... 8) -> out f32 (n*B, C, Xh, Xw): entry
+ * m * B + b is T_ks[m](frame b) at ((Xh-hk)/2, (Xw-wk)/2), (hk, wk) the member's own size, zeros elsewhere; one pass, no memset.  n in {1,2,4,8}.
+ * Even members move as rows; odd members go through an LDS tile so that both global sides run along rows.  With ks = {0} it is uf_expand_canvas /
+ * uf_frames_to_canvas bit for bit.
+ * uf_tta_merge: out = tree_sum_k T_k^-1(crop_k(y_k)) * (1/n) over the ne even members (ne*B, C, Xh, Xw) and the no odd members (no*B, C, Xoh, Xow)
+ * -- either buffer may be absent (NULL, count 0); on a square canvas they are the two halves of one model output for the batch order
+ * [0,2,4,6,1,3,5,7] -- with crop_k the member's region as uf_tta_gather placed it.  tree_sum is the balanced pairwise sum in ascending k, in f32:
+ * ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) for n = ne + no = 8; n in {1,2,4,8}, so the scale is exact.  One launch, no accumulator, no atomics.
+ * out: f32 planes (B,C,h,w), C = 1 ... 8, clamped to [0,1] when clamp01 (torch.clamp: NaN stays), or u8 frames (out_is_u8; (B,h,w,C) when out_hwc),
+ * C = 1 ... 4, through the quantiser of uf_canvas_to_frames.  With the one even member {0} it is uf_crop_clamp_canvas / uf_canvas_to_frames bit for bit.
+ * Both validate before any launch: null pointers (UF_ERR_NULL); C out of range, swap_rb with C < 3, k outside 0 ... 7, duplicate or unsorted
+ * lists, mixed parity in one list, n not in {1,2,4,8} (UF_ERR_UNSUPPORTED); a canvas smaller than a member, counts of 2^31 and more (UF_ERR_SHAPE). */
+int uf_tta_gather(const void* src, int src_is_u8, int src_hwc, int swap_rb, float* out, const int* ks, int n, int B, int C, int h, int w, int Xh, int Xw,
+                  void* stream);
+int uf_tta_merge(const float* even, const int* ks_even, int ne, int Xh, int Xw, const float* odd, const int* ks_odd, int no, int Xoh, int Xow, void* out,
+                 int out_is_u8, int out_hwc, int swap_rb, int clamp01, int B, int C, int h, int w, void* stream);
 
 /* ---- cross-modulator attention of a decoder block (LeWinTransformerBlock(cross_modulator=True), model.py:873-877, :945-949; Attention :549-595;
  * LinearProjection.forward with attn_kv :431-442), one kernel, in place on the f32 stream:

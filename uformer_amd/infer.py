@@ -276,9 +276,80 @@ def _tile_origins(ys, xs, device) -> Tensor:
     return t
 
 
+# ---------------------------------------------------------------------------------------
+# geometric self-ensemble
+# ---------------------------------------------------------------------------------------
+ENSEMBLE_MEMBERS = {8: (0, 1, 2, 3, 4, 5, 6, 7), 4: (0, 2, 4, 6), 2: (0, 4), 1: (0,)}      # members -> the transforms k of Augment_RGB_torch
+
+
+def _check_ensemble(members, canvas: str, what: str, name: str = "members"):
+    if canvas not in ("square", "rect"):
+        raise ValueError(f"{what}: canvas must be 'square' or 'rect', got {canvas!r}")
+    if isinstance(members, bool) or members not in ENSEMBLE_MEMBERS:
+        raise ValueError(f"{what}: {name} must be 8, 4, 2 or 1, got {members!r}")
+    ks = ENSEMBLE_MEMBERS[members]
+    return [k for k in ks if k % 2 == 0], [k for k in ks if k % 2]
+
+
+def _ensemble_members(model, src: Tensor, B: int, h: int, w: int, canvas: str, even, odd, max_batch: int, hwc: bool, swap_rb: bool):
+    """The restored members of ``src`` (f32 planes or uint8 frames): (even-k outputs, odd-k outputs or None).  One input buffer per canvas shape --
+    on the square canvas both parities share it, in the order [0,2,4,6,1,3,5,7] -- filled by one ``uf_tta_gather`` per parity and forwarded
+    ``max(1, max_batch // B)`` members at a time into one output buffer; a buffer that fits one forward is the model's output itself."""
+    per = max(1, int(max_batch) // B)
+    if canvas == "square":
+        X = int(math.ceil(max(h, w) / 128.0) * 128)
+        classes = [((X, X), [l for l in (even, odd) if l])]
+    else:
+        Xh, Xw = int(math.ceil(h / 128.0) * 128), int(math.ceil(w / 128.0) * 128)
+        classes = [((Xh, Xw), [even])] + ([((Xw, Xh), [odd])] if odd else [])
+    outs = []
+    for (Xa, Xb), lists in classes:
+        nm, x, m0 = sum(len(l) for l in lists), None, 0
+        for l in lists:
+            if x is None and len(l) == nm:
+                x = ops.tta_gather(src, l, Xa, Xb, hwc, swap_rb)
+            else:
+                if x is None:
+                    x = torch.empty((nm * B, src.shape[3] if hwc else src.shape[1], Xa, Xb), dtype=torch.float32, device=src.device)
+                ops.tta_gather(src, l, Xa, Xb, hwc, swap_rb, out=x[m0 * B:(m0 + len(l)) * B])
+            m0 += len(l)
+        if nm <= per:
+            y = model(x)
+        else:
+            y = None                                                 # (nm*B, in_chans, Xa, Xb): sized by the first output
+            for j0 in range(0, nm, per):
+                j1 = min(nm, j0 + per)
+                o = model(x[j0 * B:j1 * B])
+                if y is None:
+                    y = torch.empty((nm * B,) + tuple(o.shape[1:]), dtype=torch.float32, device=src.device)
+                y[j0 * B:j1 * B].copy_(o)
+        m0 = 0
+        for l in lists:
+            outs.append(y[m0 * B:(m0 + len(l)) * B])
+            m0 += len(l)
+    return outs[0], (outs[1] if odd else None)
+
+
+@torch.no_grad()
+def restore_ensemble(model, img: Tensor, canvas: str = "square", clamp: bool = True, members: int = 8, max_batch: int = 8) -> Tensor:
+    """Geometric self-ensemble, beyond the reference (the "+" variant of restoration papers): ``img`` (B,dd_in,h,w) float32 (any other dtype is converted to float32 first, as ``restore`` converts it) is restored under
+    ``members`` of the eight flips and rotations ``T_k`` = ``Augment_RGB_torch.transform<k>`` (utils/dataset_utils.py:8-33) -- 8: all; 4: k = 0, 2,
+    4, 6 (no transposed canvas); 2: k = 0, 4; 1: ``restore`` itself -- each result is turned back and the mean is clamped to [0,1]:
+    ``clamp01(tree_sum_k T_k^-1(crop(model(pad(T_k(img))))) / n)``, the sum taken pairwise in ascending k in f32 (a model that acts per pixel gets
+    its single result back bit for bit).  ``pad`` / ``crop`` are ``restore``'s for the member's own size; on ``canvas="rect"`` the odd members run
+    on the swapped canvas.  The members are a batch: one ``uf_tta_gather`` per parity builds it, the model runs ``max(1, max_batch // B)`` members
+    per forward, one ``uf_tta_merge`` turns back, sums, scales and clamps."""
+    if img.dim() != 4:
+        raise ValueError(f"restore_ensemble expects (B,C,h,w), got {tuple(img.shape)}")
+    even, odd = _check_ensemble(members, canvas, "restore_ensemble")
+    B, _, h, w = img.shape
+    ye, yo = _ensemble_members(model, img.to(torch.float32), B, h, w, canvas, even, odd, max_batch, False, False)
+    return ops.tta_merge(ye, even, yo, odd, h, w, u8=False, clamp=clamp)
+
+
 @torch.no_grad()
 def restore_frames(model, frames: Tensor, canvas: str = "square", hwc: bool = True, bgr: bool = False, tile: int = None, min_overlap: int = 128,
-                   max_batch: int = 8, out: Tensor = None) -> Tensor:
+                   max_batch: int = 8, out: Tensor = None, ensemble: int = None) -> Tensor:
     """``restore`` / ``restore_tiled`` for the pixels every caller starts and ends with: uint8 frames (B,h,w,C) (``hwc``, what a decoder hands over)
     or (B,C,h,w) on the model's device in, uint8 frames of the model's ``in_chans`` channels in the same layout out (into ``out`` when given).
     What the reference's scripts do on the host around the forward -- ``load_img``'s ``/ 255`` (utils/image_utils.py:31-35) and
@@ -288,10 +359,22 @@ def restore_frames(model, frames: Tensor, canvas: str = "square", hwc: bool = Tr
     ``tile``: frames larger than one ``tile`` x ``tile`` window (a multiple of 128) take ``restore_tiled``'s route -- the same tiles
     (``uf_tiles_gather``), forwarded ``max_batch`` at a time into one tile-output buffer, and the same cross-fade (``uf_tiles_blend``: one launch,
     no accumulator or weight-sum buffer); a frame that fits one tile takes the canvas route, as ``restore_tiled`` falls back to ``restore``
-    (on the square canvas)."""
+    (on the square canvas).
+    ``ensemble``: 8, 4, 2 or 1 members of ``restore_ensemble``, uint8 in and uint8 out through ``uf_tta_gather`` / ``uf_tta_merge``: bit for bit
+    the quantised ``restore_ensemble(model, planes, canvas=canvas, members=ensemble, clamp=False)`` of the frames divided by 255 as
+    ``uf_frames_to_canvas`` divides them (an IEEE division; ``torch.div(255)`` on the device multiplies by a reciprocal).  Not together with ``tile``."""
     B, C, h, w = _check_frames(frames, hwc, bgr, canvas, "restore_frames")
     if tile is not None and tile % 128:
         raise ValueError("restore_frames: tile must be a multiple of 128")
+    if ensemble is not None:
+        if tile is not None:
+            raise ValueError("restore_frames: ensemble and tile cannot be combined (the self-ensemble of a tiled restoration is not offered)")
+        even, odd = _check_ensemble(ensemble, canvas, "restore_frames", "ensemble")
+        out_C = int(getattr(model, "in_chans", C))                   # before any forward, as FrameRestorer checks it
+        if bgr and out_C < 3:
+            raise ValueError(f"restore_frames: bgr needs at least 3 output channels, the model gives {out_C}")
+        ye, yo = _ensemble_members(model, frames, B, h, w, canvas, even, odd, max_batch, hwc, bgr)
+        return ops.tta_merge(ye, even, yo, odd, h, w, u8=True, hwc=hwc, swap_rb=bgr, out=out)
     if tile is not None and (h > tile or w > tile):
         ys, xs = _starts(h, tile, min_overlap), _starts(w, tile, min_overlap)
         origins = _tile_origins(ys, xs, frames.device)
@@ -325,7 +408,7 @@ class FrameRestorer:
     ticket.  ``ticket.result()`` waits for that slot and returns the restored frames in the type and rank that were submitted -- a copy, or
     with ``copy=False`` a view of the pinned buffer that stays valid until the slot is used again.  A slot is reused only after its ticket has
     been consumed (``submit`` raises ``RuntimeError`` otherwise); ``map`` keeps ``depth`` frames in flight and yields results in order.
-    Results are ``restore_frames``' bit for bit.  Parameters must not change while frames are in flight (``PipelinedForward``'s rule: the
+    Results are ``restore_frames``' bit for bit (``ensemble=8``: its self-ensemble route).  Parameters must not change while frames are in flight (``PipelinedForward``'s rule: the
     operand pack is built on the caller's stream, which the slot stream waits for): ``drain()`` first.  No HIP graph is used."""
 
     MAX_DEPTH = 4      # Uformer keeps 8 workspaces by stream; the library's side streams share the hardware queues with these
@@ -349,7 +432,7 @@ class FrameRestorer:
             return t.clone() if copy else t
 
     def __init__(self, model, frame_shape, batch: int = 1, depth: int = 2, canvas: str = "rect", hwc: bool = True, bgr: bool = False, tile: int = None,
-                 min_overlap: int = 128, max_batch: int = 8, device=None):
+                 min_overlap: int = 128, max_batch: int = 8, device=None, ensemble: int = None):
         if not 1 <= int(depth) <= self.MAX_DEPTH:
             raise ValueError(f"FrameRestorer: depth must be 1 ... {self.MAX_DEPTH}, got {depth}")
         if canvas not in ("square", "rect"):
@@ -362,11 +445,15 @@ class FrameRestorer:
             raise ValueError(f"FrameRestorer: bgr needs at least 3 channels, the frames have {C}")
         if tile is not None and tile % 128:
             raise ValueError("FrameRestorer: tile must be a multiple of 128")
+        if ensemble is not None:
+            if tile is not None:
+                raise ValueError("FrameRestorer: ensemble and tile cannot be combined (the self-ensemble of a tiled restoration is not offered)")
+            _check_ensemble(ensemble, canvas, "FrameRestorer", "ensemble")
         out_C = int(getattr(model, "in_chans", C))
         if bgr and out_C < 3:
             raise ValueError(f"FrameRestorer: bgr needs at least 3 output channels, the model gives {out_C}")
         self.model, self.batch, self.depth, self.frame_shape = model, int(batch), int(depth), frame_shape
-        self._kw = dict(canvas=canvas, hwc=hwc, bgr=bgr, tile=tile, min_overlap=min_overlap, max_batch=max_batch)
+        self._kw = dict(canvas=canvas, hwc=hwc, bgr=bgr, tile=tile, min_overlap=min_overlap, max_batch=max_batch, ensemble=ensemble)
         self._in_shape = (self.batch,) + frame_shape
         self._out_shape = (self.batch,) + (frame_shape[:2] + (out_C,) if hwc else (out_C,) + frame_shape[1:])
         self._device, self.device = device, None

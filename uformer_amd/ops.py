@@ -901,6 +901,58 @@ def tiles_blend(tiles_out: Tensor, ys, xs, h: int, w: int, u8: bool = False, hwc
     return res
 
 
+def tta_gather(src: Tensor, ks, Xh: int, Xw: int, hwc: bool = False, swap_rb: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """The member batch of ``infer.restore_ensemble``: frames uint8 (divided by 255) or f32, (B,h,w,C) (``hwc``) or (B,C,h,w) -> f32
+    (len(ks)*B, C, Xh, Xw), entry m*B + b = frame b under ``T_ks[m]`` (``Augment_RGB_torch.transform<k>``), centred on the canvas, zero elsewhere.
+    ``ks``: distinct, ascending, all even or all odd (odd members are (w, h)); ``out`` receives the batch when given (a slice of a larger one)."""
+    _dev(src, out)
+    if src.dtype not in (torch.uint8, torch.float32):
+        raise UformerHipError("tta_gather: frames must be uint8 or float32")
+    B, Cc, h, w = _frame_dims(src, hwc, "tta_gather")
+    ks = [int(k) for k in ks]
+    shape = (len(ks) * B, Cc, Xh, Xw)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != src.device:
+        raise UformerHipError(f"tta_gather: out must be a contiguous float32 tensor of shape {shape} on {src.device}")
+    _launch("uf_tta_gather", src.device, _c(src), int(src.dtype == torch.uint8), int(hwc), int(swap_rb), out, (ctypes.c_int * len(ks))(*ks), len(ks),
+            B, Cc, h, w, Xh, Xw)
+    return out
+
+
+def tta_merge(even: Optional[Tensor], ks_even, odd: Optional[Tensor], ks_odd, h: int, w: int, u8: bool = False, hwc: bool = True, swap_rb: bool = False,
+              clamp: bool = True, out: Optional[Tensor] = None) -> Tensor:
+    """The mean of the restored members, each turned back: ``even`` (len(ks_even)*B, C, Xh, Xw) holds the even-k outputs, ``odd``
+    (len(ks_odd)*B, C, Xoh, Xow) the odd-k ones (either may be None with an empty list); the balanced pairwise sum in ascending k times 1/n, f32,
+    one launch.  f32 planes (B,C,h,w), clamped to [0,1] with ``clamp``; ``u8``: uint8 frames (B,h,w,C) (``hwc``) or (B,C,h,w) through
+    canvas_to_frames' quantiser."""
+    _dev(even, odd, out)
+    ks_even, ks_odd = [int(k) for k in ks_even], [int(k) for k in ks_odd]
+    ref = even if even is not None else odd
+    if ref is None or (even is None) != (not ks_even) or (odd is None) != (not ks_odd):
+        raise UformerHipError("tta_merge: a member buffer goes with a non-empty list of its transforms, and one of the two is needed")
+    n, Cc = ref.shape[0], ref.shape[1]
+    nk = len(ks_even) if even is not None else len(ks_odd)
+    B = n // nk
+    for t, ks in ((even, ks_even), (odd, ks_odd)):
+        if t is not None and (t.dim() != 4 or tuple(t.shape[:2]) != (len(ks) * B, Cc)):
+            raise UformerHipError(f"tta_merge: {tuple(t.shape)} is no batch of {len(ks)} members of {B} images with {Cc} channels")
+    if u8:
+        res = _u8_frames(B, Cc, h, w, hwc, ref.device, out, "tta_merge")
+    elif out is None:
+        res = torch.empty((B, Cc, h, w), dtype=torch.float32, device=ref.device)
+    else:
+        if out.dtype != torch.float32 or tuple(out.shape) != (B, Cc, h, w) or not out.is_contiguous() or out.device != ref.device:
+            raise UformerHipError(f"tta_merge: out must be a contiguous float32 tensor of shape {(B, Cc, h, w)} on {ref.device}")
+        res = out
+    Xh, Xw = (even.shape[2], even.shape[3]) if even is not None else (0, 0)
+    Xoh, Xow = (odd.shape[2], odd.shape[3]) if odd is not None else (0, 0)
+    _launch("uf_tta_merge", ref.device, None if even is None else _c(even, torch.float32), (ctypes.c_int * max(1, len(ks_even)))(*ks_even), len(ks_even), Xh, Xw,
+            None if odd is None else _c(odd, torch.float32), (ctypes.c_int * max(1, len(ks_odd)))(*ks_odd), len(ks_odd), Xoh, Xow,
+            res, int(u8), int(hwc), int(swap_rb), int(clamp), B, Cc, h, w)
+    return res
+
+
 def mixup(x: Tensor, lam: Tensor, perm: Tensor) -> Tensor:
     """lam[b] x[b] + (1 - lam[b]) x[perm[b]] (utils/dataset_utils.py:44-53)."""
     _dev(x, lam, perm)
